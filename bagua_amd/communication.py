@@ -756,6 +756,22 @@ def _new_comm_stream():
     return None
 
 
+def _elastic_attempt_store(world_size, timeout):
+    """Under a torchelastic agent that hosts the store, give every restart
+    attempt its own key prefix. The agent's store outlives a crashed gang,
+    and torch's env:// rendezvous adds no per-attempt prefix, so without
+    one a restarted rank can read the dead gang's gloo/RCCL addresses
+    ("connection refused") and the restart fails. None elsewhere."""
+    if os.environ.get("TORCHELASTIC_USE_AGENT_STORE") != str(True):
+        return None
+    tcp_store = dist.TCPStore(
+        os.environ["MASTER_ADDR"], int(os.environ["MASTER_PORT"]),
+        world_size, False, timeout)
+    return dist.PrefixStore(
+        "/bagua_amd/attempt_%s"
+        % os.environ.get("TORCHELASTIC_RESTART_COUNT", "0"), tcp_store)
+
+
 def init_process_group(store=None, rank: int = -1, world_size: int = -1):
     """Initialize the default process group.
 
@@ -782,6 +798,8 @@ def init_process_group(store=None, rank: int = -1, world_size: int = -1):
         if store is None:
             os.environ.setdefault("MASTER_ADDR", env.get_master_addr())
             os.environ.setdefault("MASTER_PORT", str(env.get_master_port()))
+            store = _elastic_attempt_store(world_size, timeout)
+        if store is None:
             dist.init_process_group(backend, rank=rank,
                                     world_size=world_size, timeout=timeout)
         else:

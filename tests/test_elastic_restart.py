@@ -70,3 +70,34 @@ print("FINISHED", flush=True)
     assert "INJECTED_CRASH" in out.stdout
     assert "RESUMED_FROM 1" in out.stdout, out.stdout[-2000:]
     assert "FINISHED" in out.stdout
+
+
+def test_elastic_attempt_store_prefix_carries_restart_count(monkeypatch):
+    """Under an agent-hosted store every restart attempt gets its own key
+    space; outside torchelastic the default rendezvous is left alone."""
+    from datetime import timedelta
+
+    import torch.distributed as dist
+
+    from bagua_amd.communication import _elastic_attempt_store
+
+    timeout = timedelta(seconds=20)
+    monkeypatch.delenv("TORCHELASTIC_USE_AGENT_STORE", raising=False)
+    assert _elastic_attempt_store(1, timeout) is None
+
+    agent = dist.TCPStore("127.0.0.1", 0, 1, True, timeout,
+                          wait_for_workers=False)
+    monkeypatch.setenv("MASTER_ADDR", "127.0.0.1")
+    monkeypatch.setenv("MASTER_PORT", str(agent.port))
+    monkeypatch.setenv("TORCHELASTIC_USE_AGENT_STORE", "True")
+    stores = {}
+    for attempt in ("0", "3"):
+        monkeypatch.setenv("TORCHELASTIC_RESTART_COUNT", attempt)
+        stores[attempt] = _elastic_attempt_store(1, timeout)
+        stores[attempt].set("rank_addr", "of attempt " + attempt)
+    # same key, two attempts: neither sees the other's value
+    assert stores["0"].get("rank_addr") == b"of attempt 0"
+    assert stores["3"].get("rank_addr") == b"of attempt 3"
+    assert agent.check(["/bagua_amd/attempt_0/rank_addr"])
+    assert agent.check(["/bagua_amd/attempt_3/rank_addr"])
+    assert not agent.check(["rank_addr"])
