@@ -22,6 +22,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -64,6 +65,26 @@ void bagua_fused_sgd_mixed_launch(void* p, const void* g, float* master,
                                   float dampening, float weight_decay,
                                   int nesterov, int momentum_initialized,
                                   size_t n, hipStream_t stream);
+}
+
+// moe_kernels.hip launchers
+extern "C" {
+size_t bagua_moe_assign_workspace(int S, int E);
+void bagua_moe_assign_slots_launch(const int* expert, int S, int E,
+                                   int capacity, const int* base, int* hist,
+                                   int* slot, int* counts, int* src,
+                                   hipStream_t stream);
+void bagua_moe_gather_rows_launch(int dtype, const void* x, const int* src,
+                                  void* out, const float* w, const int* dest,
+                                  int k, int S, size_t R, int M,
+                                  hipStream_t stream);
+void bagua_moe_combine_rows_launch(int dtype, const void* eo,
+                                   const int* dest, void* out,
+                                   const float* w, int k, int S, size_t R,
+                                   int M, hipStream_t stream);
+void bagua_moe_row_dot_launch(int dtype, const void* g, const void* eo,
+                              const int* dest, float* gw, int k, int S,
+                              size_t R, int M, hipStream_t stream);
 }
 
 #define HIP_CHECK(cmd)                                                    \
@@ -963,6 +984,139 @@ static void fused_adam_step(at::Tensor p, at::Tensor g, at::Tensor m,
       bc2, p.numel(), current_stream());
 }
 
+// ---------------------------------------------------------------------------
+// index-based MoE routing (moe_kernels.hip)
+// ---------------------------------------------------------------------------
+
+static constexpr int64_t kInt31 = (int64_t)1 << 31;
+
+static void check_moe_index(const at::Tensor& t, const char* what) {
+  check_device_contig(t);
+  TORCH_CHECK(t.scalar_type() == at::kInt, what, " must be int32");
+}
+
+static void check_moe_weights(const at::Tensor& t, int64_t k, int64_t S) {
+  check_device_contig(t);
+  TORCH_CHECK(t.scalar_type() == at::kFloat, "weights must be float32");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == k && t.size(1) == S,
+              "weights must have shape (k, S)");
+}
+
+// dest (k, S) with k in {1, 2}; returns k
+static int64_t check_moe_dest(const at::Tensor& dest) {
+  check_moe_index(dest, "dest");
+  TORCH_CHECK(dest.dim() == 2 && (dest.size(0) == 1 || dest.size(0) == 2),
+              "dest must have shape (k, S) with k in {1, 2}");
+  TORCH_CHECK(dest.numel() < kInt31, "S * k must be below 2^31");
+  return dest.size(0);
+}
+
+static void check_moe_rows(const at::Tensor& t, const char* what) {
+  check_device_contig(t);
+  TORCH_CHECK(t.dim() == 2, what, " must be 2-d (rows, M)");
+  TORCH_CHECK(t.size(0) < kInt31 && t.size(1) < kInt31, what,
+              ": rows and M must be below 2^31");
+}
+
+static void moe_assign_slots(at::Tensor expert, int64_t num_experts,
+                             int64_t capacity,
+                             std::optional<at::Tensor> base, at::Tensor slot,
+                             at::Tensor counts, at::Tensor src) {
+  check_moe_index(expert, "expert");
+  check_moe_index(slot, "slot");
+  check_moe_index(counts, "counts");
+  check_moe_index(src, "src");
+  TORCH_CHECK(expert.dim() == 1, "expert must be 1-d");
+  // the per-expert counters of a block live in LDS
+  TORCH_CHECK(num_experts >= 1 && num_experts <= 8192,
+              "moe_assign_slots supports 1..8192 experts");
+  TORCH_CHECK(capacity >= 1, "capacity must be positive");
+  TORCH_CHECK(expert.numel() < kInt31 / 2, "S * k must be below 2^31");
+  TORCH_CHECK(num_experts * capacity < kInt31,
+              "num_experts * capacity must be below 2^31");
+  TORCH_CHECK(slot.numel() == expert.numel(), "slot size mismatch");
+  TORCH_CHECK(counts.numel() == num_experts, "counts size mismatch");
+  TORCH_CHECK(src.numel() == num_experts * capacity, "src size mismatch");
+  const int* base_ptr = nullptr;
+  if (base.has_value()) {
+    check_moe_index(*base, "base");
+    TORCH_CHECK(base->numel() == num_experts, "base size mismatch");
+    base_ptr = (const int*)base->data_ptr();
+  }
+  const int S = (int)expert.numel(), E = (int)num_experts;
+  auto hist = at::empty({(int64_t)bagua_moe_assign_workspace(S, E)},
+                        expert.options());
+  bagua_moe_assign_slots_launch(
+      (const int*)expert.data_ptr(), S, E, (int)capacity, base_ptr,
+      (int*)hist.data_ptr(), (int*)slot.data_ptr(), (int*)counts.data_ptr(),
+      (int*)src.data_ptr(), current_stream());
+}
+
+static void moe_gather_rows(at::Tensor x, at::Tensor src, at::Tensor out,
+                            std::optional<at::Tensor> w,
+                            std::optional<at::Tensor> dest) {
+  check_moe_rows(x, "x");
+  check_moe_rows(out, "out");
+  check_moe_index(src, "src");
+  TORCH_CHECK(out.scalar_type() == x.scalar_type(), "out dtype mismatch");
+  TORCH_CHECK(src.dim() == 1 && out.size(0) == src.numel() &&
+                  out.size(1) == x.size(1), "out must be (len(src), M)");
+  const int64_t S = x.size(0);
+  const float* w_ptr = nullptr;
+  const int* dest_ptr = nullptr;
+  int64_t k = 1;
+  if (w.has_value()) {
+    TORCH_CHECK(dest.has_value(), "scaled gather needs dest");
+    k = check_moe_dest(*dest);
+    TORCH_CHECK(dest->size(1) == S, "dest must have shape (k, S)");
+    check_moe_weights(*w, k, S);
+    w_ptr = (const float*)w->data_ptr();
+    dest_ptr = (const int*)dest->data_ptr();
+  }
+  bagua_moe_gather_rows_launch(kernel_dtype(x), x.data_ptr(),
+                               (const int*)src.data_ptr(), out.data_ptr(),
+                               w_ptr, dest_ptr, (int)k, (int)S,
+                               (size_t)src.numel(), (int)x.size(1),
+                               current_stream());
+}
+
+static void moe_combine_rows(at::Tensor eo, at::Tensor dest, at::Tensor out,
+                             std::optional<at::Tensor> w) {
+  check_moe_rows(eo, "eo");
+  check_moe_rows(out, "out");
+  const int64_t k = check_moe_dest(dest);
+  const int64_t S = dest.size(1);
+  TORCH_CHECK(out.scalar_type() == eo.scalar_type(), "out dtype mismatch");
+  TORCH_CHECK(out.size(0) == S && out.size(1) == eo.size(1),
+              "out must be (S, M)");
+  const float* w_ptr = nullptr;
+  if (w.has_value()) {
+    check_moe_weights(*w, k, S);
+    w_ptr = (const float*)w->data_ptr();
+  }
+  bagua_moe_combine_rows_launch(kernel_dtype(eo), eo.data_ptr(),
+                                (const int*)dest.data_ptr(), out.data_ptr(),
+                                w_ptr, (int)k, (int)S, (size_t)eo.size(0),
+                                (int)eo.size(1), current_stream());
+}
+
+static void moe_row_dot(at::Tensor g, at::Tensor eo, at::Tensor dest,
+                        at::Tensor gw) {
+  check_moe_rows(g, "g");
+  check_moe_rows(eo, "eo");
+  const int64_t k = check_moe_dest(dest);
+  const int64_t S = dest.size(1);
+  TORCH_CHECK(g.scalar_type() == eo.scalar_type(), "g/eo dtype mismatch");
+  TORCH_CHECK(g.size(0) == S && g.size(1) == eo.size(1),
+              "g must be (S, M)");
+  check_moe_weights(gw, k, S);
+  bagua_moe_row_dot_launch(kernel_dtype(g), g.data_ptr(), eo.data_ptr(),
+                           (const int*)dest.data_ptr(),
+                           (float*)gw.data_ptr(), (int)k, (int)S,
+                           (size_t)eo.size(0), (int)g.size(1),
+                           current_stream());
+}
+
 static py::bytes nccl_unique_id() {
   ncclUniqueId id;
   NCCL_CHECK(ncclGetUniqueId(&id));
@@ -1239,4 +1393,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_sgd_step", &fused_sgd_step);
   m.def("fused_sgd_mixed_step", &fused_sgd_mixed_step);
   m.def("fused_adam_step", &fused_adam_step);
+  m.def("moe_assign_slots", &moe_assign_slots, py::arg("expert"),
+        py::arg("num_experts"), py::arg("capacity"), py::arg("base"),
+        py::arg("slot"), py::arg("counts"), py::arg("src"));
+  m.def("moe_gather_rows", &moe_gather_rows, py::arg("x"), py::arg("src"),
+        py::arg("out"), py::arg("w") = py::none(),
+        py::arg("dest") = py::none());
+  m.def("moe_combine_rows", &moe_combine_rows, py::arg("eo"),
+        py::arg("dest"), py::arg("out"), py::arg("w") = py::none());
+  m.def("moe_row_dot", &moe_row_dot);
 }

@@ -2,7 +2,11 @@
 
 ``MoE(hidden_size, expert, num_local_experts=k)`` builds
 ``num_local_experts * world_size`` experts sharded one group per rank
-(expert parallelism over the default process group)."""
+(expert parallelism over the default process group).
+
+``routing="sparse"`` moves tokens by index (HIP row kernels on GPU)
+instead of the dense (tokens, experts, capacity) einsums; results match
+the default ``"dense"`` path."""
 
 from typing import Optional
 
@@ -27,6 +31,7 @@ class MoE(torch.nn.Module):
         noisy_gate_policy: Optional[str] = None,
         drop_tokens: bool = True,
         expert_parallel_group=None,
+        routing: str = "dense",
     ):
         super().__init__()
         assert noisy_gate_policy is None or noisy_gate_policy in (
@@ -45,9 +50,10 @@ class MoE(torch.nn.Module):
         experts = Experts(expert, num_local_experts)
         gate = TopKGate(hidden_size, self.num_experts, k, capacity_factor,
                         eval_capacity_factor, min_capacity,
-                        noisy_gate_policy, drop_tokens)
+                        noisy_gate_policy, drop_tokens, routing=routing)
         self.bagua_moe = MOELayer(gate, experts, expert_parallel_group,
-                                  self.ep_size, num_local_experts)
+                                  self.ep_size, num_local_experts,
+                                  routing=routing)
         self.dropout = torch.nn.Dropout(output_dropout_prob)
 
     def forward(self, hidden_states, used_token=None):

@@ -16,6 +16,13 @@ Token flow per layer: gate -> dispatch einsum -> alltoall over the
 expert-parallel group -> local experts -> alltoall back -> combine
 einsum. On one 8xMI355X node the two alltoalls are single-hop xGMI
 exchanges (fully-connected point-to-point topology).
+
+``routing="sparse"`` replaces the two einsums over the
+(tokens, experts, capacity) tensor by index-based row movement: the
+gates (``top1routing`` / ``top2routing``) emit a ``RoutingPlan`` of
+integer destination rows and per-choice weights, and
+``bagua_amd.ops.moe`` dispatches and combines rows directly (HIP kernels
+on GPU). Gate math, RNG stream and results match the dense path.
 """
 
 import math
@@ -26,6 +33,11 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch import Tensor
 from torch.nn import Module
+
+from ...ops import moe as moe_ops
+from ...ops.moe import RoutingPlan
+
+ROUTINGS = ("dense", "sparse")
 
 uniform_map = {}
 gumbel_map = {}
@@ -221,6 +233,99 @@ def top2gating(
     return l_aux, combine_weights, dispatch_mask, exp_counts
 
 
+def top1routing(
+    logits: Tensor,
+    capacity_factor: float,
+    min_capacity: int,
+    used_token: Optional[Tensor] = None,
+    noisy_gate_policy: Optional[str] = None,
+    drop_tokens: bool = True,
+) -> Tuple[Tensor, RoutingPlan, Tensor]:
+    """Top-1 gating as a routing plan. Same arguments, RNG use and
+    results as ``top1gating``; returns (l_aux, plan, exp_counts) without
+    building any (tokens, experts, capacity) tensor."""
+    if not drop_tokens:
+        raise ValueError("sparse routing requires drop_tokens=True")
+    if noisy_gate_policy == "RSample":
+        logits_w_noise = logits + gumbel_rsample(logits.shape,
+                                                 device=logits.device)
+    gates = F.softmax(logits, dim=1)
+    num_tokens, num_experts = gates.shape
+    capacity = _capacity(num_tokens, num_experts, capacity_factor,
+                         min_capacity)
+
+    indices1_s = torch.argmax(
+        logits_w_noise if noisy_gate_policy == "RSample" else gates, dim=1)
+    expert1 = indices1_s.int()
+    if used_token is not None:
+        expert1 = torch.where(used_token.reshape(-1) != 0, expert1,
+                              torch.full_like(expert1, -1))
+
+    slot1, counts1, src = moe_ops.assign_slots(expert1, num_experts,
+                                               capacity)
+
+    # auxiliary load-balancing loss (GShard eq. 4); counts1 / num_tokens
+    # is the mean of the (masked) one-hot choice
+    me = torch.mean(gates, dim=0)
+    ce = counts1.float() / num_tokens
+    l_aux = torch.sum(me * ce) * num_experts
+
+    keep1 = (slot1 >= 0) & (slot1 < capacity)
+    gates1_s = gates.gather(1, indices1_s.unsqueeze(1)).squeeze(1) * keep1
+    dest1 = torch.where(keep1, expert1 * capacity + slot1,
+                        torch.full_like(slot1, -1))
+    exp_counts = counts1.long().clamp(max=capacity)
+    plan = RoutingPlan(dest1.unsqueeze(0), gates1_s.unsqueeze(0), src,
+                       num_experts, capacity)
+    return l_aux, plan, exp_counts
+
+
+def top2routing(
+    logits: Tensor, capacity_factor: float, min_capacity: int,
+) -> Tuple[Tensor, RoutingPlan, Tensor]:
+    """Top-2 gating as a routing plan. Same arguments, RNG use and
+    results as ``top2gating``; returns (l_aux, plan, exp_counts)."""
+    gates = F.softmax(logits, dim=1)
+    num_tokens, num_experts = gates.shape
+    capacity = _capacity(num_tokens, num_experts, 2 * capacity_factor,
+                         min_capacity)
+
+    expert1 = torch.argmax(gates, dim=1)
+    noised = logits + gumbel_rsample(logits.shape, device=logits.device)
+    noised = noised.scatter(1, expert1.unsqueeze(1), float("-inf"))
+    expert2 = torch.argmax(noised, dim=1)
+
+    # first choices fill every queue before any second choice: the
+    # second call starts each queue at the first call's count
+    e1, e2 = expert1.int(), expert2.int()
+    slot1, counts1, src = moe_ops.assign_slots(e1, num_experts, capacity)
+    slot2, counts2, src = moe_ops.assign_slots(e2, num_experts, capacity,
+                                               base=counts1, src=src)
+
+    l_aux = torch.mean(gates.mean(dim=0) * (counts1.float() / num_tokens)) \
+        * num_experts * num_experts
+
+    keep1 = slot1 < capacity
+    keep2 = slot2 < capacity
+
+    # renormalize the surviving pair weights to sum to one
+    w1 = gates.gather(1, expert1.unsqueeze(1)).squeeze(1) * keep1
+    w2 = gates.gather(1, expert2.unsqueeze(1)).squeeze(1) * keep2
+    denom = torch.clamp(w1 + w2, min=torch.finfo(gates.dtype).eps)
+    w1 = w1 / denom
+    w2 = w2 / denom
+
+    drop = torch.full_like(slot1, -1)
+    dest = torch.stack([torch.where(keep1, e1 * capacity + slot1, drop),
+                        torch.where(keep2, e2 * capacity + slot2, drop)])
+    c1, c2 = counts1.long(), counts2.long()
+    exp_counts = c1.clamp(max=capacity) \
+        + torch.minimum(c2, (capacity - c1).clamp(min=0))
+    plan = RoutingPlan(dest, torch.stack([w1, w2]), src, num_experts,
+                       capacity)
+    return l_aux, plan, exp_counts
+
+
 class TopKGate(Module):
     """Learned router (reference: sharded_moe.py:93-303)."""
 
@@ -228,10 +333,17 @@ class TopKGate(Module):
                  capacity_factor: float = 1.0,
                  eval_capacity_factor: float = 1.0, min_capacity: int = 4,
                  noisy_gate_policy: Optional[str] = None,
-                 drop_tokens: bool = True):
+                 drop_tokens: bool = True, routing: str = "dense"):
         super().__init__()
         if k not in (1, 2):
             raise ValueError("Only top-1 and top-2 gatings are supported")
+        if routing not in ROUTINGS:
+            raise ValueError("routing must be one of %s, got %r"
+                             % (ROUTINGS, routing))
+        if routing == "sparse" and not drop_tokens:
+            raise ValueError(
+                "routing='sparse' requires drop_tokens=True")
+        self.routing = routing
         self.wg = torch.nn.Linear(model_dim, num_experts, bias=False)
         self.k = k
         self.capacity_factor = capacity_factor
@@ -248,20 +360,29 @@ class TopKGate(Module):
         logits = F.linear(input_fp32, self.wg.weight.float())
         cap = (self.capacity_factor if self.training
                else self.eval_capacity_factor)
+        sparse = self.routing == "sparse"
         if self.k == 1:
-            return top1gating(
+            return (top1routing if sparse else top1gating)(
                 logits, cap, self.min_capacity, used_token,
                 self.noisy_gate_policy if self.training else None,
                 self.drop_tokens)
-        return top2gating(logits, cap, self.min_capacity)
+        return (top2routing if sparse else top2gating)(
+            logits, cap, self.min_capacity)
 
 
 class MOELayer(Module):
     """Mixture-of-experts layer (reference: sharded_moe.py:306-375)."""
 
     def __init__(self, gate: TopKGate, experts: Module, ep_group,
-                 ep_size: int, num_local_experts: int):
+                 ep_size: int, num_local_experts: int,
+                 routing: str = "dense"):
         super().__init__()
+        if routing not in ROUTINGS:
+            raise ValueError("routing must be one of %s, got %r"
+                             % (ROUTINGS, routing))
+        if routing != getattr(gate, "routing", "dense"):
+            raise ValueError("gate and layer must use the same routing")
+        self.routing = routing
         self.gate = gate
         self.experts = experts
         self.ep_group = ep_group
@@ -274,6 +395,10 @@ class MOELayer(Module):
     def forward(self, *input: Tensor, **kwargs) -> Tensor:
         d_model = input[0].shape[-1]
         reshaped_input = input[0].reshape(-1, d_model)
+
+        if self.routing == "sparse":
+            return self._forward_sparse(input[0], reshaped_input,
+                                        kwargs.get("used_token"))
 
         self.l_aux, combine_weights, dispatch_mask, self.exp_counts = \
             self.gate(reshaped_input, kwargs.get("used_token"))
@@ -295,3 +420,23 @@ class MOELayer(Module):
             "sec,ecm->sm", combine_weights.to(expert_output.dtype),
             expert_output)
         return combined.reshape(input[0].shape)
+
+    def _forward_sparse(self, input: Tensor, reshaped_input: Tensor,
+                        used_token: Optional[Tensor]) -> Tensor:
+        d_model = reshaped_input.shape[-1]
+        self.l_aux, plan, self.exp_counts = self.gate(reshaped_input,
+                                                      used_token)
+
+        dispatched = moe_ops.dispatch(reshaped_input, plan)
+        dispatched = dispatched.reshape(self.num_experts, -1, d_model)
+
+        dispatched = _AllToAll.apply(self.ep_group, dispatched)
+        dispatched = dispatched.reshape(
+            self.ep_size, self.num_local_experts, -1, d_model)
+
+        expert_output = self.experts(dispatched)
+        expert_output = _AllToAll.apply(self.ep_group, expert_output)
+        expert_output = expert_output.reshape(-1, d_model)
+
+        combined = moe_ops.combine(expert_output, plan)
+        return combined.reshape(input.shape)

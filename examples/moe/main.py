@@ -34,7 +34,7 @@ from bagua_amd.parallel.moe import MoE
 
 
 class MoEMnistNet(nn.Module):
-    def __init__(self, num_local_experts: int):
+    def __init__(self, num_local_experts: int, routing: str = "dense"):
         super().__init__()
         self.conv1 = nn.Conv2d(1, 32, 3, 1)
         self.conv2 = nn.Conv2d(32, 64, 3, 1)
@@ -43,7 +43,7 @@ class MoEMnistNet(nn.Module):
             hidden_size=128,
             expert=nn.Sequential(nn.Linear(128, 512), nn.ReLU(),
                                  nn.Linear(512, 128)),
-            num_local_experts=num_local_experts, k=1)
+            num_local_experts=num_local_experts, k=1, routing=routing)
         self.fc2 = nn.Linear(128, 10)
 
     def forward(self, x):
@@ -60,6 +60,10 @@ def main():
     parser.add_argument("--steps", type=int, default=50)
     parser.add_argument("--batch-size", type=int, default=64)
     parser.add_argument("--ckpt-dir", type=str, default="")
+    parser.add_argument("--routing", choices=["dense", "sparse"],
+                        default="dense",
+                        help="token movement: dense einsums or index-based "
+                             "HIP row kernels")
     args = parser.parse_args()
 
     use_cuda = torch.cuda.is_available()
@@ -69,7 +73,7 @@ def main():
     bagua_amd.init_process_group()
 
     torch.manual_seed(13)
-    model = MoEMnistNet(args.num_local_experts).to(device)
+    model = MoEMnistNet(args.num_local_experts, args.routing).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=1e-3)
     ddp = bagua_amd.DistributedDataParallel(
         model, optimizers=[optimizer],
