@@ -115,8 +115,13 @@ def dequant_reduce(buf: torch.Tensor, flat: torch.Tensor, num_chunks: int,
                                     average)
         return
     if _use_native(buf, flat):  # beyond the kernel's LDS param table
-        decompress_chunked_into(buf, flat, num_chunks)
-        reduce_chunk_inplace(flat, num_chunks, target_chunk, average)
+        # unfused chain in a scratch bucket, so that like the fused kernel
+        # (and the CPU path) only flat's target chunk is written
+        tmp = torch.empty_like(flat)
+        decompress_chunked_into(buf, tmp, num_chunks)
+        reduce_chunk_inplace(tmp, num_chunks, target_chunk, average)
+        flat.view(num_chunks, -1)[target_chunk].copy_(
+            tmp.view(num_chunks, -1)[target_chunk])
         return
     chunk = flat.numel() // num_chunks
     dec = quant.decompress_chunked(buf, num_chunks, chunk, flat.dtype)

@@ -57,9 +57,11 @@ void bagua_fused_sgd_launch(float* p, const float* g, float* m, float lr,
                             int momentum_initialized, size_t n,
                             hipStream_t stream);
 void bagua_fused_adam_launch(float* p, const float* g, float* m, float* v,
-                             float lr, float beta1, float beta2, float eps,
-                             float weight_decay, int adamw, float bc1,
-                             float bc2, size_t n, hipStream_t stream);
+                             float lr, float beta1, float beta2,
+                             float one_minus_beta1, float one_minus_beta2,
+                             float eps, float weight_decay, int adamw,
+                             float bc1, float bc2, size_t n,
+                             hipStream_t stream);
 void bagua_fused_sgd_mixed_launch(void* p, const void* g, float* master,
                                   float* m, float lr, float momentum,
                                   float dampening, float weight_decay,
@@ -975,13 +977,18 @@ static void fused_adam_step(at::Tensor p, at::Tensor g, at::Tensor m,
                             double weight_decay, bool adamw) {
   check_device_contig(p);
   TORCH_CHECK(p.scalar_type() == at::kFloat, "fused Adam needs f32 master");
-  float bc1 = 1.f - (float)std::pow(beta1, (double)step);
-  float bc2 = 1.f - (float)std::pow(beta2, (double)step);
+  // in double, cast once: 1.f - (float)pow(beta2, step) and the kernel's
+  // former 1.f - beta2 each lose 1.3e-5 relative at beta2 = 0.999 (the
+  // subtraction cancels). At step 1 the two errors cancelled each other
+  // in v/bc2, later they did not; both are formed here now.
+  float bc1 = (float)(1.0 - std::pow(beta1, (double)step));
+  float bc2 = (float)(1.0 - std::pow(beta2, (double)step));
   bagua_fused_adam_launch(
       (float*)p.data_ptr(), (const float*)g.data_ptr(),
       (float*)m.data_ptr(), (float*)v.data_ptr(), (float)lr, (float)beta1,
-      (float)beta2, (float)eps, (float)weight_decay, adamw ? 1 : 0, bc1,
-      bc2, p.numel(), current_stream());
+      (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
+      (float)weight_decay, adamw ? 1 : 0, bc1, bc2, p.numel(),
+      current_stream());
 }
 
 // ---------------------------------------------------------------------------

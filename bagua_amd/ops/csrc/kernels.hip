@@ -18,9 +18,11 @@
 //
 // Compression wire format (matches bagua_amd/ops/quant.py, the numerics
 // oracle): per chunk a 32-byte header whose first 8 bytes are (min,max)
-// as float32, then ceil32(chunk) uint8 payload.
+// as float32 and whose bytes 8..31 are zero, then chunk uint8 payload
+// bytes, then zero padding up to ceil32(chunk). quantize_kernel writes
+// every byte of the chunk regions it is asked for.
 //   scale = 255/(max-min+1e-7); upper = rint(max*scale);
-//   lower = upper-255; q = min(rint(x*scale), upper) - lower.
+//   lower = upper-255; q = clamp(min(rint(x*scale), upper) - lower, 0, 255).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -301,6 +303,15 @@ __device__ __forceinline__ void quant_params(float mn, float mx,
   lower = upper - 255.0f;
 }
 
+// level - lower leaves [0, 255] by a few units when |x|*scale > 2^24
+// (constant chunks, |mean| >> range): the f32 roundings of level and
+// lower then disagree; a minimum on a rounding tie (min = -max) gives -1.
+// Clamp before the cast, which wraps (256 -> 0, -1 -> 255) and would
+// decode one extreme as the other; no in-range value changes.
+__device__ __forceinline__ uint8_t quant_level_u8(float q) {
+  return (uint8_t)fminf(fmaxf(q, 0.0f), 255.0f);
+}
+
 // grid.y = chunk; writes 32B header (min,max float32) + payload
 template <typename T>
 __global__ void quantize_kernel(const T* __restrict__ x, size_t chunk,
@@ -326,6 +337,12 @@ __global__ void quantize_kernel(const T* __restrict__ x, size_t chunk,
   }
   const T* __restrict__ src = x + (size_t)c * chunk;
   uint8_t* __restrict__ payload = dst + 32;
+  // same reason for the padding behind the payload (bytes 32+chunk ..
+  // chunk_stride, at most 31 of them): callers hand in torch.empty wires
+  if (blockIdx.x == 0) {
+    const size_t pad = chunk_stride - 32 - chunk;
+    if (threadIdx.x < pad) payload[chunk + threadIdx.x] = 0;
+  }
 
   // per-T width (measured, gpurun r2c9): 16-byte tensor-side loads win;
   // widening the u8 store granule beyond that costs ~1%
@@ -341,7 +358,7 @@ __global__ void quantize_kernel(const T* __restrict__ x, size_t chunk,
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       float level = fminf(rintf(to_f(a.v[k]) * scale), upper);
-      q[k] = (uint8_t)(level - lower);
+      q[k] = quant_level_u8(level - lower);
     }
     if (V == 4)
       *reinterpret_cast<uint32_t*>(payload + i * 4) =
@@ -352,7 +369,7 @@ __global__ void quantize_kernel(const T* __restrict__ x, size_t chunk,
   }
   for (size_t i = nv * V + tid; i < chunk; i += stride) {
     float level = fminf(rintf(to_f(src[i]) * scale), upper);
-    payload[i] = (uint8_t)(level - lower);
+    payload[i] = quant_level_u8(level - lower);
   }
 }
 
@@ -767,12 +784,17 @@ __global__ void fused_sgd_kernel(float* __restrict__ p,
   }
 }
 
-// Adam / AdamW (torch semantics, bias-corrected)
+// Adam / AdamW (torch semantics, bias-corrected). 1 - beta and the bias
+// corrections come from the host, formed in double and cast once: in f32
+// 1.f - 0.999f is off by 1.3e-5 relative (the subtraction cancels), which
+// sqrt(v) carries into every update.
 __global__ void fused_adam_kernel(float* __restrict__ p,
                                   const float* __restrict__ g,
                                   float* __restrict__ m,
                                   float* __restrict__ v, float lr,
-                                  float beta1, float beta2, float eps,
+                                  float beta1, float beta2,
+                                  float one_minus_beta1,
+                                  float one_minus_beta2, float eps,
                                   float weight_decay, int adamw,
                                   float bias_correction1,
                                   float bias_correction2, size_t n) {
@@ -804,8 +826,8 @@ __global__ void fused_adam_kernel(float* __restrict__ p,
           param *= (1.f - lr * weight_decay);
         else
           grad += weight_decay * param;
-        float mi = beta1 * mm[k] + (1.f - beta1) * grad;
-        float vi = beta2 * uu[k] + (1.f - beta2) * grad * grad;
+        float mi = beta1 * mm[k] + one_minus_beta1 * grad;
+        float vi = beta2 * uu[k] + one_minus_beta2 * grad * grad;
         mm[k] = mi;
         uu[k] = vi;
         float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
@@ -823,8 +845,8 @@ __global__ void fused_adam_kernel(float* __restrict__ p,
       param *= (1.f - lr * weight_decay);
     else
       grad += weight_decay * param;
-    float mi = beta1 * m[i] + (1.f - beta1) * grad;
-    float vi = beta2 * v[i] + (1.f - beta2) * grad * grad;
+    float mi = beta1 * m[i] + one_minus_beta1 * grad;
+    float vi = beta2 * v[i] + one_minus_beta2 * grad * grad;
     m[i] = mi;
     v[i] = vi;
     float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
@@ -930,13 +952,15 @@ void bagua_fused_sgd_mixed_launch(void* p, const void* g, float* master,
 }
 
 void bagua_fused_adam_launch(float* p, const float* g, float* m, float* v,
-                             float lr, float beta1, float beta2, float eps,
-                             float weight_decay, int adamw, float bc1,
-                             float bc2, size_t n, hipStream_t stream) {
+                             float lr, float beta1, float beta2,
+                             float one_minus_beta1, float one_minus_beta2,
+                             float eps, float weight_decay, int adamw,
+                             float bc1, float bc2, size_t n,
+                             hipStream_t stream) {
   int grid = grid_for(n / 8 + 1);
   hipLaunchKernelGGL(fused_adam_kernel, dim3(grid), dim3(BLOCK), 0, stream,
-                     p, g, m, v, lr, beta1, beta2, eps, weight_decay,
-                     adamw, bc1, bc2, n);
+                     p, g, m, v, lr, beta1, beta2, one_minus_beta1,
+                     one_minus_beta2, eps, weight_decay, adamw, bc1, bc2, n);
 }
 
 }  // extern "C"

@@ -7,8 +7,13 @@ and the golden Python model in tests/internal/compressor.py:4-33):
     scale       = 255 / (max - min + 1e-7)
     upper_bound = rint(max * scale)
     lower_bound = upper_bound - 255
-    q           = clamp(rint(x * scale), max=upper_bound) - lower_bound   (uint8)
+    q           = clamp(rint(x * scale), max=upper_bound) - lower_bound
+    q           = clamp(q, 0, 255)                                    (uint8)
     x'          = (q + lower_bound) / scale
+
+The second clamp is this project's addition: in f32 the first line can
+leave [0, 255] by a few units when |x|*scale exceeds 2**24, and the uint8
+cast would then wrap (see ``compress``).
 
 This module is the CPU executor's compressor and the numerics oracle for
 the hand-written CDNA4 HIP kernels (tests compare bitwise on the uint8
@@ -21,22 +26,40 @@ EPS = 1e-7
 LEVELS = 255.0
 
 
+def _scale(_min: torch.Tensor, _max: torch.Tensor) -> torch.Tensor:
+    """255 / (max - min + 1e-7) as ONE correctly rounded f32 division, as
+    quant_params in kernels.hip forms it. ``LEVELS / tensor`` is not that:
+    torch evaluates a Python scalar over a tensor as
+    ``tensor.reciprocal() * scalar``, two roundings, which is 1 ulp off
+    the quotient for about a quarter of all chunks and moves a payload
+    level wherever x*scale sits that close to a tie (every element once
+    |x|*scale > 2**24)."""
+    d = _max - _min + EPS
+    return torch.full_like(d, LEVELS) / d
+
+
 def compress(tensor: torch.Tensor):
     """Compress a 1-D tensor. Returns (minmax[2] float32, payload uint8)."""
     t = tensor.float()
     _min, _max = t.min(), t.max()
-    scale = LEVELS / (_max - _min + EPS)
+    scale = _scale(_min, _max)
     upper = torch.round(_max * scale)
     lower = upper - LEVELS
     level = torch.clamp(torch.round(t * scale), max=upper)
     minmax = torch.stack([_min, _max]).to(torch.float32)
-    return minmax, (level - lower).to(torch.uint8)
+    # |x|*scale >> 2**24 (constant chunks, |mean| >> range) makes the f32
+    # roundings of level and lower disagree by a few units, which puts
+    # level - lower just outside [0, 255]; an unclamped uint8 cast wraps
+    # the maximum element to 0 (decoded as the minimum). The clamp fires
+    # on no other input, so every in-range payload is bitwise unchanged.
+    q = torch.clamp(level - lower, min=0.0, max=LEVELS)
+    return minmax, q.to(torch.uint8)
 
 
 def decompress(minmax: torch.Tensor, payload: torch.Tensor,
                dtype=torch.float32) -> torch.Tensor:
     _min, _max = minmax[0].float(), minmax[1].float()
-    scale = LEVELS / (_max - _min + EPS)
+    scale = _scale(_min, _max)
     upper = torch.round(_max * scale)
     lower = upper - LEVELS
     return ((payload.float() + lower) / scale).to(dtype)
@@ -45,8 +68,12 @@ def decompress(minmax: torch.Tensor, payload: torch.Tensor,
 # ---------------------------------------------------------------------------
 # Chunked wire format (matches the native kernels): per chunk, a 32-byte
 # header holding min,max ALWAYS as float32 (bytes 8..31 zero), then the
-# uint8 payload. Deliberate deviation from the reference's layout, which
-# stores min/max in the SOURCE dtype (datatypes/mod.rs:700-777): a fixed
+# uint8 payload, then zero padding up to the next multiple of 32 bytes.
+# Every byte of a written chunk region is defined: the native kernel
+# zeroes the header tail and the padding itself, so a wire allocated
+# with torch.empty is bitwise equal to this oracle's. Deliberate
+# deviation from the reference's layout, which stores min/max in the
+# SOURCE dtype (datatypes/mod.rs:700-777): a fixed
 # f32 header keeps one kernel per dtype and loses no precision for
 # f16/bf16 inputs. Wire-incompatible with the reference by design.
 # ---------------------------------------------------------------------------
@@ -79,7 +106,11 @@ def compress_chunked(tensor: torch.Tensor, num_chunks: int,
         minmax, payload = compress(flat.narrow(0, c * chunk, chunk))
         hdr = out.narrow(0, c * stride, HEADER_BYTES)
         hdr[:8].view(torch.float32).copy_(minmax)
+        hdr[8:].zero_()
         out.narrow(0, c * stride + HEADER_BYTES, chunk).copy_(payload)
+        # padding of a caller-supplied ``out`` is zeroed like the kernel's
+        out.narrow(0, c * stride + HEADER_BYTES + chunk,
+                   stride - HEADER_BYTES - chunk).zero_()
     return out
 
 

@@ -61,6 +61,71 @@ def test_matches_torch_gpu(fused_cls, ref_cls, kwargs):
     assert torch.allclose(ref, out, atol=1e-5), "fused kernel deviates"
 
 
+@pytest.mark.gpu
+@pytest.mark.skipif(not torch.cuda.is_available(), reason="needs MI355X")
+def test_fused_adam_first_step_vs_float64():
+    """FusedAdam step 1, default betas, against torch.optim.Adam run in
+    float64 on the CPU from the same f32 parameters and gradients.
+
+    Bound |out - ref| <= k * eps32 * mag, eps32 = 2**-23, mag the sum of
+    the absolute values of the formula's terms, k the f32 roundings of
+    fused_adam_kernel without weight decay:
+      exp_avg_sq  beta2*v + (1-beta2)*g*g: casts of beta2 and 1-beta2,
+                  three multiplies, add: k = 6, mag = (1-beta2)*g*g
+      param       p - lr*(1/bc1)*m/(sqrt(v)*rsqrt(bc2) + eps): casts of lr
+                  and bc1, reciprocal, two multiplies, divide, subtract
+                  (7); m = beta1*m + (1-beta1)*g (5); the denominator's
+                  casts of bc2 and eps, rsqrtf, sqrtf, multiply, add and
+                  half of v's error (6 + 3): k = 21, mag = |p| + |step|
+    The parameters are scaled down so that |step| = lr governs mag: the
+    bias corrections and 1-beta2 formed in f32 are off by 1.3e-5 relative
+    (110 eps32), far outside the bound on exp_avg_sq; at step 1 alone the
+    two errors cancel in the parameter update, from step 2 on they do not
+    (tests/test_gpu_bucket_kernels.py steps 2 and 10)."""
+    eps32 = 2.0 ** -23
+    m_gpu = _model()
+    with torch.no_grad():
+        for p in m_gpu.parameters():
+            p.mul_(1e-3)
+    m_gpu = m_gpu.cuda()
+    m_ref = copy.deepcopy(m_gpu).cpu().double()
+    opt = FusedAdam(m_gpu.parameters(), lr=1e-2)
+    ref_opt = torch.optim.Adam(m_ref.parameters(), lr=1e-2)
+
+    torch.manual_seed(34)
+    x = torch.randn(6, 10, device="cuda")
+    y = torch.randn(6, 5, device="cuda")
+    opt.zero_grad()
+    ((m_gpu(x) - y) ** 2).mean().backward()
+    p0 = [p.detach().double().cpu().clone() for p in m_gpu.parameters()]
+    for p, q in zip(m_gpu.parameters(), m_ref.parameters()):
+        q.grad = p.grad.detach().double().cpu().clone()
+    opt.step()
+    ref_opt.step()
+    torch.cuda.synchronize()
+
+    out = torch.cat([p.detach().double().cpu().reshape(-1)
+                     for p in m_gpu.parameters()])
+    ref = torch.cat([q.detach().reshape(-1) for q in m_ref.parameters()])
+    start = torch.cat([p.reshape(-1) for p in p0])
+    mag = start.abs() + (ref - start).abs()
+    err = (out - ref).abs()
+    print("BOUND FusedAdam step 1 p: worst %.3f of the k=21 bound"
+          % float((err / (21 * eps32 * mag)).max()))
+    assert bool((err <= 21 * eps32 * mag).all()), (
+        "param off by %g" % float((err / (eps32 * mag)).max()))
+
+    v_out = opt._flat[0]["exp_avg_sq"].double().cpu()
+    v_ref = torch.cat([ref_opt.state[q]["exp_avg_sq"].reshape(-1)
+                       for q in m_ref.parameters()])
+    v_err = (v_out - v_ref).abs()
+    print("BOUND FusedAdam step 1 exp_avg_sq: worst %.3f of the k=6 bound"
+          % float((v_err / (6 * eps32 * v_ref).clamp(min=1e-300)).max()))
+    assert bool((v_err <= 6 * eps32 * v_ref).all()), (
+        "exp_avg_sq off by %g eps32"
+        % float((v_err / (eps32 * v_ref).clamp(min=1e-300)).max()))
+
+
 def test_bf16_master_matches_fp32_cpu():
     """Pure-bf16 FusedSGD (fp32 master) must track plain fp32 SGD within
     bf16 rounding of the weights."""

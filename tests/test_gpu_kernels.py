@@ -94,25 +94,27 @@ def test_compress_matches_golden(dtype, num_chunks, chunk):
     x = (torch.randn(num_chunks * chunk, device="cuda") * 3).to(dtype)
 
     stride = quant.compressed_chunk_bytes(chunk)
-    out = torch.zeros(stride * num_chunks, dtype=torch.uint8, device="cuda")
+    # the kernel must define every wire byte itself
+    out = torch.full((stride * num_chunks,), 0xFF, dtype=torch.uint8,
+                     device="cuda")
     _C.compress_chunked(x, out, num_chunks, -1)
     torch.cuda.synchronize()
 
-    gold = quant.compress_chunked(x.float(), num_chunks)
+    # the oracle runs on the CPU, where every f32 operation (the division
+    # in scale above all) is correctly rounded like the kernel's
+    gold = quant.compress_chunked(x.float().cpu(), num_chunks).cuda()
     # headers: min/max stored as f32 from the input dtype's values
     for c in range(num_chunks):
         hdr = out[c * stride:c * stride + 8].view(torch.float32)
         ghdr = gold[c * stride:c * stride + 8].view(torch.float32)
-        assert torch.allclose(hdr, ghdr, atol=1e-6), "chunk %d header" % c
+        assert torch.equal(hdr, ghdr), "chunk %d header" % c
         payload = out[c * stride + 32:c * stride + 32 + chunk]
         gpayload = gold[c * stride + 32:c * stride + 32 + chunk]
         diff = (payload.int() - gpayload.int()).abs()
-        # float->dtype->float rounding can move rint by 1 level for
-        # f16/bf16; f32 must be exact
-        if dtype == torch.float32:
-            assert int(diff.max()) == 0
-        else:
-            assert int(diff.max()) <= 1
+        # x.float() is exact for f16/bf16, and both sides do the same f32
+        # operations on it: every dtype must match exactly
+        assert int(diff.max()) == 0
+    assert torch.equal(out, gold), "header tail or padding"
 
     # roundtrip through native decompress
     y = torch.zeros_like(x)
