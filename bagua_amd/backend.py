@@ -99,6 +99,12 @@ class BaguaBackend:
                         "duplicate tensor data_ptr for %s" % t.name)
                 ptrs.add(p)
             b.reset_ready()
+            # decided here once, not per autograd hook call: a bucket
+            # whose ops are all identities is never read, so the engine
+            # leaves its tensors' gradients where autograd put them
+            unread = bool(b.ops) and self._is_identity_at_world1(b)
+            for t in b.tensors:
+                t.bucket_unread = unread
         self.ordered_buckets = list(buckets)
         self._tensor_names = names
         self._queue_idx = 0

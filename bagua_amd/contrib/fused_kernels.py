@@ -4,9 +4,10 @@ with one hand-written CDNA4 HIP kernel per group.
 MI355X-native addition beyond the reference's contiguity fusion
 (contrib/fused_optimizer.py): parameters and state are flattened once at
 construction, then every step is a single memory-bound kernel
-(ops/csrc/kernels.hip fused_sgd_kernel / fused_adam_kernel) instead of
-the foreach optimizer's 3-5 launches per group. Math matches
-torch.optim.SGD / Adam / AdamW exactly (tests/test_fused_kernels.py).
+(ops/csrc/kernels.hip fused_segments_kernel) instead of the foreach
+optimizer's 3-5 launches per group. Gradients are read in place, never
+gathered. Math matches torch.optim.SGD / Adam / AdamW exactly
+(tests/test_fused_kernels.py).
 
 CPU fallback runs the same math in torch, so the optimizers are usable
 (and testable) everywhere.
@@ -20,7 +21,10 @@ from ..ops import native
 
 
 class _FlatGroupOptimizer(torch.optim.Optimizer):
-    """Flattens each param group into (flat_param, flat_grad) views."""
+    """Flattens each param group's weights (and state) once. Gradients
+    are not flattened: the GPU kernels read each ``p.grad`` where it lives
+    (a bucket view, a fresh autograd tensor, or None), through the
+    segmented entry points of the extension."""
 
     def _flatten_group(self, group):
         params = [p for p in group["params"] if p.requires_grad]
@@ -29,29 +33,37 @@ class _FlatGroupOptimizer(torch.optim.Optimizer):
         total = sum(p.numel() for p in params)
         p0 = params[0]
         flat_w = torch.zeros(total, dtype=p0.dtype, device=p0.device)
-        flat_g = torch.zeros_like(flat_w)
-        offset = 0
+        offsets = [0]
         for p in params:
-            w_view = flat_w.narrow(0, offset, p.numel()).view_as(p)
+            w_view = flat_w.narrow(0, offsets[-1], p.numel()).view_as(p)
             w_view.copy_(p.detach())
             p.data = w_view
-            g_view = flat_g.narrow(0, offset, p.numel()).view_as(p)
-            if p.grad is not None:
-                g_view.copy_(p.grad.detach())
-            p.grad = g_view
-            p._bagua_grad_view = g_view
-            offset += p.numel()
-        return {"params": params, "flat_w": flat_w, "flat_g": flat_g}
+            offsets.append(offsets[-1] + p.numel())
+        return {"params": params, "flat_w": flat_w, "offsets": offsets}
 
-    def _repair_grads(self, rec):
+    @staticmethod
+    def _segment_grads(rec):
+        """The live grads, one per segment, as the kernels take them:
+        None stays None (a zero gradient); a grad of another dtype or
+        layout is made conforming for its segment only."""
+        dtype = rec["flat_w"].dtype
+        grads = []
         for p in rec["params"]:
-            view = p._bagua_grad_view
-            if p.grad is None:
-                view.zero_()
-                p.grad = view
-            elif p.grad.data_ptr() != view.data_ptr():
-                view.copy_(p.grad.detach())
-                p.grad = view
+            g = p.grad
+            if g is not None and (g.dtype != dtype
+                                  or not g.is_contiguous()):
+                g = g.detach().to(dtype).contiguous()
+            grads.append(g)
+        return grads
+
+    @staticmethod
+    def _gathered_grad(rec):
+        """All grads in one flat tensor (CPU fallback)."""
+        w = rec["flat_w"]
+        return torch.cat([
+            (p.grad.detach().to(w.dtype) if p.grad is not None
+             else torch.zeros_like(p)).reshape(-1)
+            for p in rec["params"]])
 
     # flat-group state lives outside optimizer.state; (de)serialize it so
     # checkpointing (bagua_amd.checkpoint) round-trips momentum/master
@@ -117,27 +129,27 @@ class FusedSGD(_FlatGroupOptimizer):
         for group, rec in zip(self.param_groups, self._flat):
             if rec is None:
                 continue
-            self._repair_grads(rec)
-            w, g = rec["flat_w"], rec["flat_g"]
+            w = rec["flat_w"]
             mu = group["momentum"]
             m = rec.get("momentum_buffer")
             master = rec.get("master")
             if w.is_cuda and native.available() \
                     and w.dtype == torch.float32:
-                native.lib().fused_sgd_step(
-                    w, g, m if m is not None else g, group["lr"], mu,
-                    group["dampening"], group["weight_decay"],
-                    group["nesterov"],
+                native.lib().fused_sgd_step_segments(
+                    w, self._segment_grads(rec), rec["offsets"], m,
+                    group["lr"], mu, group["dampening"],
+                    group["weight_decay"], group["nesterov"],
                     rec.get("momentum_initialized", False))
             elif w.is_cuda and native.available() \
                     and w.dtype == torch.bfloat16:
-                native.lib().fused_sgd_mixed_step(
-                    w, g, master, m if m is not None else master,
+                native.lib().fused_sgd_mixed_step_segments(
+                    w, self._segment_grads(rec), rec["offsets"], master, m,
                     group["lr"], mu, group["dampening"],
                     group["weight_decay"], group["nesterov"],
                     rec.get("momentum_initialized", False))
             else:
                 ref = master if master is not None else w
+                g = self._gathered_grad(rec)
                 grad = g.float() if master is not None else g
                 if group["weight_decay"] != 0:
                     grad = grad.add(ref, alpha=group["weight_decay"])
@@ -182,20 +194,21 @@ class FusedAdam(_FlatGroupOptimizer):
         for group, rec in zip(self.param_groups, self._flat):
             if rec is None:
                 continue
-            self._repair_grads(rec)
             rec["step"] += 1
-            w, g = rec["flat_w"], rec["flat_g"]
+            w = rec["flat_w"]
             m, v = rec["exp_avg"], rec["exp_avg_sq"]
             master = rec.get("master")
             beta1, beta2 = group["betas"]
             if w.is_cuda and native.available() \
                     and w.dtype == torch.float32:
-                native.lib().fused_adam_step(
-                    w, g, m, v, rec["step"], group["lr"], beta1, beta2,
-                    group["eps"], group["weight_decay"], group["adamw"])
+                native.lib().fused_adam_step_segments(
+                    w, self._segment_grads(rec), rec["offsets"], m, v,
+                    rec["step"], group["lr"], beta1, beta2, group["eps"],
+                    group["weight_decay"], group["adamw"])
             else:
                 # bf16 params: update the fp32 master, write back bf16
                 ref = master if master is not None else w
+                g = self._gathered_grad(rec)
                 grad = g.float() if master is not None else g
                 if group["adamw"]:
                     ref.mul_(1 - group["lr"] * group["weight_decay"])

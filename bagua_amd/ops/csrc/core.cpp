@@ -67,6 +67,25 @@ void bagua_fused_sgd_mixed_launch(void* p, const void* g, float* master,
                                   float dampening, float weight_decay,
                                   int nesterov, int momentum_initialized,
                                   size_t n, hipStream_t stream);
+void bagua_fused_sgd_segments_launch(float* p, float* m, float lr,
+                                     float momentum, float dampening,
+                                     float weight_decay, int nesterov,
+                                     int momentum_initialized,
+                                     const void* const* grads,
+                                     const size_t* begins,
+                                     const size_t* numels, size_t count,
+                                     hipStream_t stream);
+void bagua_fused_sgd_mixed_segments_launch(
+    void* p, float* master, float* m, float lr, float momentum,
+    float dampening, float weight_decay, int nesterov,
+    int momentum_initialized, const void* const* grads, const size_t* begins,
+    const size_t* numels, size_t count, hipStream_t stream);
+void bagua_fused_adam_segments_launch(
+    float* p, float* m, float* v, float lr, float beta1, float beta2,
+    float one_minus_beta1, float one_minus_beta2, float eps,
+    float weight_decay, int adamw, float bc1, float bc2,
+    const void* const* grads, const size_t* begins, const size_t* numels,
+    size_t count, hipStream_t stream);
 }
 
 // moe_kernels.hip launchers
@@ -991,6 +1010,109 @@ static void fused_adam_step(at::Tensor p, at::Tensor g, at::Tensor m,
       current_stream());
 }
 
+// Segmented steps: the flat tensors as above, but the gradient is read
+// where it lives. grads[k] covers flat elements [offsets[k], offsets[k+1]);
+// None there is a zero gradient.
+struct GradSegments {
+  std::vector<const void*> grads;
+  std::vector<size_t> begins, numels;
+};
+
+static GradSegments check_segments(
+    const at::Tensor& p, const std::vector<std::optional<at::Tensor>>& grads,
+    const std::vector<int64_t>& offsets) {
+  check_device_contig(p);
+  TORCH_CHECK(offsets.size() == grads.size() + 1,
+              "need len(grads) + 1 offsets");
+  TORCH_CHECK(offsets.front() == 0 && offsets.back() == p.numel(),
+              "segments must tile [0, numel)");
+  GradSegments s;
+  for (size_t k = 0; k < grads.size(); ++k) {
+    const int64_t n = offsets[k + 1] - offsets[k];
+    TORCH_CHECK(n >= 0, "segment offsets must ascend");
+    const void* ptr = nullptr;
+    if (grads[k].has_value()) {
+      const at::Tensor& g = *grads[k];
+      check_device_contig(g);
+      TORCH_CHECK(g.device() == p.device(), "grad ", k, " on another device");
+      TORCH_CHECK(g.scalar_type() == p.scalar_type(), "grad ", k,
+                  " dtype differs from the parameters'");
+      TORCH_CHECK(g.numel() == n, "grad ", k, " has ", g.numel(),
+                  " elements, its segment ", n);
+      ptr = g.data_ptr();
+    }
+    if (n == 0) continue;
+    s.grads.push_back(ptr);
+    s.begins.push_back((size_t)offsets[k]);
+    s.numels.push_back((size_t)n);
+  }
+  return s;
+}
+
+static float* check_flat_state(const std::optional<at::Tensor>& t,
+                               const at::Tensor& p, bool needed,
+                               const char* what) {
+  if (!needed) return nullptr;
+  TORCH_CHECK(t.has_value(), what, " is missing");
+  check_device_contig(*t);
+  TORCH_CHECK(t->device() == p.device() && t->scalar_type() == at::kFloat &&
+                  t->numel() == p.numel(),
+              what, " must be f32, on the parameters' device and of their "
+              "size");
+  return (float*)t->data_ptr();
+}
+
+static void fused_sgd_step_segments(
+    at::Tensor p, std::vector<std::optional<at::Tensor>> grads,
+    std::vector<int64_t> offsets, std::optional<at::Tensor> m, double lr,
+    double momentum, double dampening, double weight_decay, bool nesterov,
+    bool momentum_initialized) {
+  TORCH_CHECK(p.scalar_type() == at::kFloat, "fused SGD needs f32 master");
+  const GradSegments s = check_segments(p, grads, offsets);
+  float* mp = check_flat_state(m, p, momentum != 0.0, "momentum buffer");
+  bagua_fused_sgd_segments_launch(
+      (float*)p.data_ptr(), mp, (float)lr, (float)momentum, (float)dampening,
+      (float)weight_decay, nesterov ? 1 : 0, momentum_initialized ? 1 : 0,
+      s.grads.data(), s.begins.data(), s.numels.data(), s.grads.size(),
+      current_stream());
+}
+
+static void fused_sgd_mixed_step_segments(
+    at::Tensor p, std::vector<std::optional<at::Tensor>> grads,
+    std::vector<int64_t> offsets, at::Tensor master,
+    std::optional<at::Tensor> m, double lr, double momentum,
+    double dampening, double weight_decay, bool nesterov,
+    bool momentum_initialized) {
+  TORCH_CHECK(p.scalar_type() == at::kBFloat16, "params must be bf16");
+  const GradSegments s = check_segments(p, grads, offsets);
+  float* master_p = check_flat_state(master, p, true, "master");
+  float* mp = check_flat_state(m, p, momentum != 0.0, "momentum buffer");
+  bagua_fused_sgd_mixed_segments_launch(
+      p.data_ptr(), master_p, mp, (float)lr, (float)momentum,
+      (float)dampening, (float)weight_decay, nesterov ? 1 : 0,
+      momentum_initialized ? 1 : 0, s.grads.data(), s.begins.data(),
+      s.numels.data(), s.grads.size(), current_stream());
+}
+
+static void fused_adam_step_segments(
+    at::Tensor p, std::vector<std::optional<at::Tensor>> grads,
+    std::vector<int64_t> offsets, at::Tensor m, at::Tensor v, int64_t step,
+    double lr, double beta1, double beta2, double eps, double weight_decay,
+    bool adamw) {
+  TORCH_CHECK(p.scalar_type() == at::kFloat, "fused Adam needs f32 master");
+  const GradSegments s = check_segments(p, grads, offsets);
+  float* mp = check_flat_state(m, p, true, "exp_avg");
+  float* vp = check_flat_state(v, p, true, "exp_avg_sq");
+  // bias corrections and 1 - beta as in fused_adam_step
+  float bc1 = (float)(1.0 - std::pow(beta1, (double)step));
+  float bc2 = (float)(1.0 - std::pow(beta2, (double)step));
+  bagua_fused_adam_segments_launch(
+      (float*)p.data_ptr(), mp, vp, (float)lr, (float)beta1, (float)beta2,
+      (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
+      (float)weight_decay, adamw ? 1 : 0, bc1, bc2, s.grads.data(),
+      s.begins.data(), s.numels.data(), s.grads.size(), current_stream());
+}
+
 // ---------------------------------------------------------------------------
 // index-based MoE routing (moe_kernels.hip)
 // ---------------------------------------------------------------------------
@@ -1400,6 +1522,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_sgd_step", &fused_sgd_step);
   m.def("fused_sgd_mixed_step", &fused_sgd_mixed_step);
   m.def("fused_adam_step", &fused_adam_step);
+  m.def("fused_sgd_step_segments", &fused_sgd_step_segments, py::arg("p"),
+        py::arg("grads"), py::arg("offsets"), py::arg("m"), py::arg("lr"),
+        py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"),
+        py::arg("nesterov"), py::arg("momentum_initialized"));
+  m.def("fused_sgd_mixed_step_segments", &fused_sgd_mixed_step_segments,
+        py::arg("p"), py::arg("grads"), py::arg("offsets"),
+        py::arg("master"), py::arg("m"), py::arg("lr"), py::arg("momentum"),
+        py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"),
+        py::arg("momentum_initialized"));
+  m.def("fused_adam_step_segments", &fused_adam_step_segments, py::arg("p"),
+        py::arg("grads"), py::arg("offsets"), py::arg("m"), py::arg("v"),
+        py::arg("step"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("weight_decay"), py::arg("adamw"));
   m.def("moe_assign_slots", &moe_assign_slots, py::arg("expert"),
         py::arg("num_experts"), py::arg("capacity"), py::arg("base"),
         py::arg("slot"), py::arg("counts"), py::arg("src"));

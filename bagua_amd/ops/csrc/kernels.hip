@@ -727,6 +727,58 @@ void bagua_dequant_reduce_launch(int dtype, const uint8_t* in, void* x,
 // kernel).
 // ---------------------------------------------------------------------------
 
+// Per-element arithmetic, one function per optimizer: the flat and the
+// segmented kernels call it on their vector and scalar paths alike. Every
+// fused multiply-add is written out and contraction is switched off, so
+// the rounding does not depend on what the compiler makes of the code
+// around a call: that is what keeps all those paths bitwise equal. (Left
+// to the compiler, momentum * m + (1 - dampening) * grad came out as three
+// different instruction sequences in three call sites.)
+
+// SGD with momentum/dampening/nesterov/weight-decay (torch semantics).
+// m is read only when momentum_initialized, written when momentum != 0.
+__device__ __forceinline__ void sgd_update(float& w, float g, float& m,
+                                           float lr, float momentum,
+                                           float dampening,
+                                           float weight_decay, int nesterov,
+                                           int momentum_initialized) {
+#pragma clang fp contract(off)
+  float grad = fmaf(weight_decay, w, g);
+  float upd = grad;
+  if (momentum != 0.f) {
+    float buf = momentum_initialized
+                    ? fmaf(1.f - dampening, grad, momentum * m)
+                    : grad;
+    m = buf;
+    upd = nesterov ? fmaf(momentum, buf, grad) : buf;
+  }
+  w = fmaf(-lr, upd, w);
+}
+
+// Adam / AdamW (torch semantics, bias-corrected)
+__device__ __forceinline__ void adam_update(float& w, float g, float& m,
+                                            float& v, float lr, float beta1,
+                                            float beta2,
+                                            float one_minus_beta1,
+                                            float one_minus_beta2, float eps,
+                                            float weight_decay, int adamw,
+                                            float inv_bc1,
+                                            float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  float param = w;
+  float grad = g;
+  if (adamw)
+    param *= fmaf(-lr, weight_decay, 1.f);
+  else
+    grad = fmaf(weight_decay, param, grad);
+  float mi = fmaf(beta1, m, one_minus_beta1 * grad);
+  float vi = fmaf(beta2, v, one_minus_beta2 * grad * grad);
+  m = mi;
+  v = vi;
+  float denom = fmaf(sqrtf(vi), inv_sqrt_bc2, eps);
+  w = param - lr * inv_bc1 * mi / denom;
+}
+
 extern "C" {
 
 // SGD with momentum/dampening/nesterov/weight-decay (torch semantics)
@@ -754,33 +806,20 @@ __global__ void fused_sgd_kernel(float* __restrict__ p,
       const float* gg = &gv.x;
       float* mm = &mv.x;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float grad = gg[k] + weight_decay * pp[k];
-        float upd = grad;
-        if (momentum != 0.f) {
-          float buf = momentum_initialized
-                          ? momentum * mm[k] + (1.f - dampening) * grad
-                          : grad;
-          mm[k] = buf;
-          upd = nesterov ? grad + momentum * buf : buf;
-        }
-        pp[k] -= lr * upd;
-      }
+      for (int k = 0; k < 4; ++k)
+        sgd_update(pp[k], gg[k], mm[k], lr, momentum, dampening,
+                   weight_decay, nesterov, momentum_initialized);
       p4[idx] = pv;
       if (momentum != 0.f) m4[idx] = mv;
     }
   }
   for (size_t i = nv * 8 + tid; i < n; i += stride) {
-    float grad = g[i] + weight_decay * p[i];
-    float upd = grad;
-    if (momentum != 0.f) {
-      float buf = momentum_initialized
-                      ? momentum * m[i] + (1.f - dampening) * grad
-                      : grad;
-      m[i] = buf;
-      upd = nesterov ? grad + momentum * buf : buf;
-    }
-    p[i] -= lr * upd;
+    float w = p[i];
+    float mi = momentum != 0.f && momentum_initialized ? m[i] : 0.f;
+    sgd_update(w, g[i], mi, lr, momentum, dampening, weight_decay, nesterov,
+               momentum_initialized);
+    p[i] = w;
+    if (momentum != 0.f) m[i] = mi;
   }
 }
 
@@ -819,38 +858,19 @@ __global__ void fused_adam_kernel(float* __restrict__ p,
       float* mm = &mv.x;
       float* uu = &vv.x;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float param = pp[k];
-        float grad = gg[k];
-        if (adamw)
-          param *= (1.f - lr * weight_decay);
-        else
-          grad += weight_decay * param;
-        float mi = beta1 * mm[k] + one_minus_beta1 * grad;
-        float vi = beta2 * uu[k] + one_minus_beta2 * grad * grad;
-        mm[k] = mi;
-        uu[k] = vi;
-        float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        pp[k] = param - lr * inv_bc1 * mi / denom;
-      }
+      for (int k = 0; k < 4; ++k)
+        adam_update(pp[k], gg[k], mm[k], uu[k], lr, beta1, beta2,
+                    one_minus_beta1, one_minus_beta2, eps, weight_decay,
+                    adamw, inv_bc1, inv_sqrt_bc2);
       p4[idx] = pv;
       m4[idx] = mv;
       v4[idx] = vv;
     }
   }
   for (size_t i = nv * 8 + tid; i < n; i += stride) {
-    float param = p[i];
-    float grad = g[i];
-    if (adamw)
-      param *= (1.f - lr * weight_decay);
-    else
-      grad += weight_decay * param;
-    float mi = beta1 * m[i] + one_minus_beta1 * grad;
-    float vi = beta2 * v[i] + one_minus_beta2 * grad * grad;
-    m[i] = mi;
-    v[i] = vi;
-    float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-    p[i] = param - lr * inv_bc1 * mi / denom;
+    adam_update(p[i], g[i], m[i], v[i], lr, beta1, beta2, one_minus_beta1,
+                one_minus_beta2, eps, weight_decay, adamw, inv_bc1,
+                inv_sqrt_bc2);
   }
 }
 
@@ -900,19 +920,10 @@ __global__ void fused_sgd_mixed_kernel(__hip_bfloat16* __restrict__ p,
     for (int k = 0; k < 8; ++k) {
       float* ww = &w[k / 4].x;
       float* mm = &mb[k / 4].x;
-      float wk = ww[k % 4];
-      float grad = __bfloat162float(gv.v[k]) + weight_decay * wk;
-      float upd = grad;
-      if (momentum != 0.f) {
-        float buf = momentum_initialized
-                        ? momentum * mm[k % 4] + (1.f - dampening) * grad
-                        : grad;
-        mm[k % 4] = buf;
-        upd = nesterov ? grad + momentum * buf : buf;
-      }
-      wk -= lr * upd;
-      ww[k % 4] = wk;
-      pv.v[k] = __float2bfloat16(wk);
+      sgd_update(ww[k % 4], __bfloat162float(gv.v[k]), mm[k % 4], lr,
+                 momentum, dampening, weight_decay, nesterov,
+                 momentum_initialized);
+      pv.v[k] = __float2bfloat16(ww[k % 4]);
     }
     ma4[2 * i] = w[0];
     ma4[2 * i + 1] = w[1];
@@ -924,17 +935,11 @@ __global__ void fused_sgd_mixed_kernel(__hip_bfloat16* __restrict__ p,
   }
   for (size_t i = nv * 8 + tid; i < n; i += stride) {
     float w = master[i];
-    float grad = __bfloat162float(g[i]) + weight_decay * w;
-    float upd = grad;
-    if (momentum != 0.f) {
-      float buf = momentum_initialized
-                      ? momentum * m[i] + (1.f - dampening) * grad
-                      : grad;
-      m[i] = buf;
-      upd = nesterov ? grad + momentum * buf : buf;
-    }
-    w -= lr * upd;
+    float mi = momentum != 0.f && momentum_initialized ? m[i] : 0.f;
+    sgd_update(w, __bfloat162float(g[i]), mi, lr, momentum, dampening,
+               weight_decay, nesterov, momentum_initialized);
     master[i] = w;
+    if (momentum != 0.f) m[i] = mi;
     p[i] = __float2bfloat16(w);
   }
 }
@@ -961,6 +966,368 @@ void bagua_fused_adam_launch(float* p, const float* g, float* m, float* v,
   hipLaunchKernelGGL(fused_adam_kernel, dim3(grid), dim3(BLOCK), 0, stream,
                      p, g, m, v, lr, beta1, beta2, one_minus_beta1,
                      one_minus_beta2, eps, weight_decay, adamw, bc1, bc2, n);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// segmented fused steps: weights, master and optimizer state stay flat and
+// are accessed exactly as above; only the gradient is read where it lives
+// (a bucket view, a fresh autograd tensor, or nowhere at all), through a
+// table of segments {grad, begin, numel} in flat-element space. That saves
+// the gather of every gradient into a flat copy before each step.
+//
+// The table travels by value in the kernel arguments (no device-side
+// table, no copy, nothing to allocate: the step stays graph-capturable);
+// more than SEG_CAP segments take several launches. A launch covers the
+// flat range [begin of its first segment, end of its last) and grid-
+// strides over the 8-element flat vectors that overlap it. A vector that
+// lies inside one segment and inside the range takes the vector path of
+// the flat kernels, with the gradient vector-loaded when its address is
+// 16-byte aligned and element by element otherwise. A vector that
+// straddles two segments or the range's edge goes element-wise; there are
+// at most two of those per segment. A null grad pointer is a zero
+// gradient.
+// ---------------------------------------------------------------------------
+
+#define SEG_CAP 128  // 128 x 24 B + the op's scalars < 4 KB of kernel args
+
+struct GradSeg {
+  const void* grad;  // null: zero gradient
+  size_t begin;      // flat element offset
+  size_t numel;      // > 0
+};
+
+struct SegTable {
+  GradSeg seg[SEG_CAP];  // contiguous in flat space, ascending
+  int count;
+};
+
+// A gradient pointer comes out of the table, so the compiler cannot see
+// that it points to global memory, as it can for a kernel argument. Saying
+// so keeps the gradient loads global loads and not flat ones. Gradients
+// are read as raw elements: float, or the 16 bits of a bf16.
+#define GLOBAL_AS __attribute__((address_space(1)))
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef unsigned short u16x8_t __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ float grad_to_f(float v) { return v; }
+__device__ __forceinline__ float grad_to_f(unsigned short bf16_bits) {
+  return __uint_as_float((unsigned)bf16_bits << 16);
+}
+
+__device__ __forceinline__ void load_grad8(const float GLOBAL_AS* g,
+                                           float (&out)[8]) {
+  const f32x4_t a = reinterpret_cast<const f32x4_t GLOBAL_AS*>(g)[0];
+  const f32x4_t b = reinterpret_cast<const f32x4_t GLOBAL_AS*>(g)[1];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    out[k] = a[k];
+    out[4 + k] = b[k];
+  }
+}
+
+__device__ __forceinline__ void load_grad8(const unsigned short GLOBAL_AS* g,
+                                           float (&out)[8]) {
+  const u16x8_t a = *reinterpret_cast<const u16x8_t GLOBAL_AS*>(g);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) out[k] = grad_to_f(a[k]);
+}
+
+// f32 weights, f32 grads
+struct SgdSegOp {
+  using grad_t = float;
+  float* p;
+  float* m;
+  float lr, momentum, dampening, weight_decay;
+  int nesterov, momentum_initialized;
+
+  // Flat vector i8 (elements 8*i8 .. 8*i8+7, all inside the range) in two
+  // halves, so that the kernel can issue the flat loads before it branches
+  // on where the gradient is: load(), then finish() with the gradient.
+  struct Vec {
+    float4 w[2], mb[2];
+  };
+
+  __device__ __forceinline__ void load(size_t i8, Vec& s) const {
+    const float4* p4 = reinterpret_cast<const float4*>(p) + 2 * i8;
+    const float4* m4 = reinterpret_cast<const float4*>(m) + 2 * i8;
+    s.w[0] = p4[0];
+    s.w[1] = p4[1];
+    if (momentum != 0.f && momentum_initialized) {
+      s.mb[0] = m4[0];
+      s.mb[1] = m4[1];
+    }
+  }
+
+  __device__ __forceinline__ void finish(size_t i8, Vec& s,
+                                         const float (&g)[8]) const {
+    float4* p4 = reinterpret_cast<float4*>(p) + 2 * i8;
+    float4* m4 = reinterpret_cast<float4*>(m) + 2 * i8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      sgd_update((&s.w[k / 4].x)[k % 4], g[k], (&s.mb[k / 4].x)[k % 4], lr,
+                 momentum, dampening, weight_decay, nesterov,
+                 momentum_initialized);
+    p4[0] = s.w[0];
+    p4[1] = s.w[1];
+    if (momentum != 0.f) {
+      m4[0] = s.mb[0];
+      m4[1] = s.mb[1];
+    }
+  }
+
+  __device__ __forceinline__ void one(size_t i, float g) const {
+    float w = p[i];
+    float mi = momentum != 0.f && momentum_initialized ? m[i] : 0.f;
+    sgd_update(w, g, mi, lr, momentum, dampening, weight_decay, nesterov,
+               momentum_initialized);
+    p[i] = w;
+    if (momentum != 0.f) m[i] = mi;
+  }
+};
+
+// bf16 weights + f32 master, bf16 grads
+struct SgdMixedSegOp {
+  using grad_t = unsigned short;  // bf16 bits
+  __hip_bfloat16* p;
+  float* master;
+  float* m;
+  float lr, momentum, dampening, weight_decay;
+  int nesterov, momentum_initialized;
+
+  struct Vec {
+    float4 w[2], mb[2];
+  };
+
+  __device__ __forceinline__ void load(size_t i8, Vec& s) const {
+    const float4* ma4 = reinterpret_cast<const float4*>(master) + 2 * i8;
+    const float4* m4 = reinterpret_cast<const float4*>(m) + 2 * i8;
+    s.w[0] = ma4[0];
+    s.w[1] = ma4[1];
+    if (momentum != 0.f && momentum_initialized) {
+      s.mb[0] = m4[0];
+      s.mb[1] = m4[1];
+    }
+  }
+
+  __device__ __forceinline__ void finish(size_t i8, Vec& s,
+                                         const float (&g)[8]) const {
+    float4* ma4 = reinterpret_cast<float4*>(master) + 2 * i8;
+    float4* m4 = reinterpret_cast<float4*>(m) + 2 * i8;
+    Vec16<__hip_bfloat16> pv;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      sgd_update((&s.w[k / 4].x)[k % 4], g[k], (&s.mb[k / 4].x)[k % 4], lr,
+                 momentum, dampening, weight_decay, nesterov,
+                 momentum_initialized);
+      pv.v[k] = __float2bfloat16((&s.w[k / 4].x)[k % 4]);
+    }
+    ma4[0] = s.w[0];
+    ma4[1] = s.w[1];
+    if (momentum != 0.f) {
+      m4[0] = s.mb[0];
+      m4[1] = s.mb[1];
+    }
+    reinterpret_cast<Vec16<__hip_bfloat16>*>(p)[i8] = pv;
+  }
+
+  __device__ __forceinline__ void one(size_t i, float g) const {
+    float w = master[i];
+    float mi = momentum != 0.f && momentum_initialized ? m[i] : 0.f;
+    sgd_update(w, g, mi, lr, momentum, dampening, weight_decay, nesterov,
+               momentum_initialized);
+    master[i] = w;
+    if (momentum != 0.f) m[i] = mi;
+    p[i] = __float2bfloat16(w);
+  }
+};
+
+// f32 weights, f32 grads
+struct AdamSegOp {
+  using grad_t = float;
+  float* p;
+  float* m;
+  float* v;
+  float lr, beta1, beta2, one_minus_beta1, one_minus_beta2, eps;
+  float weight_decay, bias_correction1, bias_correction2;
+  int adamw;
+
+  struct Vec {
+    float4 w[2], mb[2], vb[2];
+  };
+
+  __device__ __forceinline__ void load(size_t i8, Vec& s) const {
+    const float4* p4 = reinterpret_cast<const float4*>(p) + 2 * i8;
+    const float4* m4 = reinterpret_cast<const float4*>(m) + 2 * i8;
+    const float4* v4 = reinterpret_cast<const float4*>(v) + 2 * i8;
+    s.w[0] = p4[0];
+    s.w[1] = p4[1];
+    s.mb[0] = m4[0];
+    s.mb[1] = m4[1];
+    s.vb[0] = v4[0];
+    s.vb[1] = v4[1];
+  }
+
+  __device__ __forceinline__ void finish(size_t i8, Vec& s,
+                                         const float (&g)[8]) const {
+    float4* p4 = reinterpret_cast<float4*>(p) + 2 * i8;
+    float4* m4 = reinterpret_cast<float4*>(m) + 2 * i8;
+    float4* v4 = reinterpret_cast<float4*>(v) + 2 * i8;
+    // formed on the device, as in fused_adam_kernel
+    const float inv_bc1 = 1.f / bias_correction1;
+    const float inv_sqrt_bc2 = rsqrtf(bias_correction2);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      adam_update((&s.w[k / 4].x)[k % 4], g[k], (&s.mb[k / 4].x)[k % 4],
+                  (&s.vb[k / 4].x)[k % 4], lr, beta1, beta2,
+                  one_minus_beta1, one_minus_beta2, eps, weight_decay, adamw,
+                  inv_bc1, inv_sqrt_bc2);
+    p4[0] = s.w[0];
+    p4[1] = s.w[1];
+    m4[0] = s.mb[0];
+    m4[1] = s.mb[1];
+    v4[0] = s.vb[0];
+    v4[1] = s.vb[1];
+  }
+
+  __device__ __forceinline__ void one(size_t i, float g) const {
+    const float inv_bc1 = 1.f / bias_correction1;
+    const float inv_sqrt_bc2 = rsqrtf(bias_correction2);
+    adam_update(p[i], g, m[i], v[i], lr, beta1, beta2, one_minus_beta1,
+                one_minus_beta2, eps, weight_decay, adamw, inv_bc1,
+                inv_sqrt_bc2);
+  }
+};
+
+template <typename Op>
+__global__ void __launch_bounds__(BLOCK)
+fused_segments_kernel(Op op, SegTable tab) {
+  using G = typename Op::grad_t;
+  // the table is indexed per lane below, so it is staged in LDS first
+  __shared__ size_t s_begin[SEG_CAP + 1];
+  __shared__ const G* s_grad[SEG_CAP];
+  const int count = tab.count;
+  if ((int)threadIdx.x < count) {
+    const GradSeg sg = tab.seg[threadIdx.x];
+    s_begin[threadIdx.x] = sg.begin;
+    s_grad[threadIdx.x] = static_cast<const G*>(sg.grad);
+    if ((int)threadIdx.x == count - 1) s_begin[count] = sg.begin + sg.numel;
+  }
+  __syncthreads();
+  const size_t lo = s_begin[0], hi = s_begin[count];
+  const size_t v_end = (hi + 7) / 8;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  // current segment [sb, se), kept across iterations: the search runs
+  // again only when a lane's next vector has left it
+  int s = 0;
+  size_t sb = lo, se = s_begin[1];
+  const G* sg = s_grad[0];
+  for (size_t i8 = lo / 8 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i8 < v_end; i8 += stride) {
+    const size_t i0 = i8 * 8;
+    const size_t first = i0 > lo ? i0 : lo;  // first element in range
+    if (first >= se) {
+      int a = s + 1, b = count - 1;  // last segment with begin <= first
+      while (a < b) {
+        const int mid = (a + b + 1) >> 1;
+        if (s_begin[mid] <= first) a = mid; else b = mid - 1;
+      }
+      s = a;
+      sb = s_begin[s];
+      se = s_begin[s + 1];
+      sg = s_grad[s];
+    }
+    if (i0 >= lo && i0 + 8 <= se) {  // inside the range and one segment
+      // flat loads first: they are then in flight while the gradient's
+      // are, whichever branch below loads it
+      typename Op::Vec st;
+      op.load(i8, st);
+      float g[8];
+      if (sg == nullptr) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) g[k] = 0.f;
+      } else {
+        const G GLOBAL_AS* gp = (const G GLOBAL_AS*)sg + (i0 - sb);
+        if (((uintptr_t)gp & 15) == 0) {
+          load_grad8(gp, g);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) g[k] = grad_to_f(gp[k]);
+        }
+      }
+      op.finish(i8, st, g);
+    } else {
+      // element by element; t walks on from the current segment
+      int t = s;
+      const size_t last = i0 + 8 < hi ? i0 + 8 : hi;
+      for (size_t i = first; i < last; ++i) {
+        while (i >= s_begin[t + 1]) ++t;
+        const G GLOBAL_AS* gp = (const G GLOBAL_AS*)s_grad[t];
+        op.one(i, gp != nullptr ? grad_to_f(gp[i - s_begin[t]]) : 0.f);
+      }
+    }
+  }
+}
+
+// launches over consecutive runs of at most SEG_CAP segments
+template <typename Op>
+static void launch_segments(const Op& op, const void* const* grads,
+                            const size_t* begins, const size_t* numels,
+                            size_t count, hipStream_t stream) {
+  for (size_t base = 0; base < count; base += SEG_CAP) {
+    SegTable tab;
+    tab.count = (int)(count - base < SEG_CAP ? count - base : SEG_CAP);
+    for (int k = 0; k < tab.count; ++k)
+      tab.seg[k] = GradSeg{grads[base + k], begins[base + k],
+                           numels[base + k]};
+    const size_t lo = tab.seg[0].begin;
+    const size_t hi = tab.seg[tab.count - 1].begin +
+                      tab.seg[tab.count - 1].numel;
+    const int grid = grid_for((hi + 7) / 8 - lo / 8);
+    hipLaunchKernelGGL((fused_segments_kernel<Op>), dim3(grid), dim3(BLOCK),
+                       0, stream, op, tab);
+  }
+}
+
+extern "C" {
+
+// Segment k covers flat elements [begins[k], begins[k] + numels[k]); the
+// segments are non-empty, ascending and contiguous (the caller checks).
+
+void bagua_fused_sgd_segments_launch(float* p, float* m, float lr,
+                                     float momentum, float dampening,
+                                     float weight_decay, int nesterov,
+                                     int momentum_initialized,
+                                     const void* const* grads,
+                                     const size_t* begins,
+                                     const size_t* numels, size_t count,
+                                     hipStream_t stream) {
+  const SgdSegOp op{p, m, lr, momentum, dampening, weight_decay, nesterov,
+                    momentum_initialized};
+  launch_segments(op, grads, begins, numels, count, stream);
+}
+
+void bagua_fused_sgd_mixed_segments_launch(
+    void* p, float* master, float* m, float lr, float momentum,
+    float dampening, float weight_decay, int nesterov,
+    int momentum_initialized, const void* const* grads, const size_t* begins,
+    const size_t* numels, size_t count, hipStream_t stream) {
+  const SgdMixedSegOp op{(__hip_bfloat16*)p, master, m, lr, momentum,
+                         dampening, weight_decay, nesterov,
+                         momentum_initialized};
+  launch_segments(op, grads, begins, numels, count, stream);
+}
+
+void bagua_fused_adam_segments_launch(
+    float* p, float* m, float* v, float lr, float beta1, float beta2,
+    float one_minus_beta1, float one_minus_beta2, float eps,
+    float weight_decay, int adamw, float bc1, float bc2,
+    const void* const* grads, const size_t* begins, const size_t* numels,
+    size_t count, hipStream_t stream) {
+  const AdamSegOp op{p, m, v, lr, beta1, beta2, one_minus_beta1,
+                     one_minus_beta2, eps, weight_decay, bc1, bc2, adamw};
+  launch_segments(op, grads, begins, numels, count, stream);
 }
 
 }  // extern "C"

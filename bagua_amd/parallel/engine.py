@@ -358,7 +358,7 @@ class BaguaDistributedDataParallel:
                 if not self.require_backward_grad_sync:
                     return
                 bt = self._bagua_tensor_map.get(name)
-                if bt is not None:
+                if bt is not None and not bt.bucket_unread:
                     bt.repair_bucket_view()
                 backward_hook(name, param)
                 if not self._is_post_backward_callback_queued:
@@ -384,7 +384,12 @@ class BaguaDistributedDataParallel:
             backward_hook = self.bagua_algorithm.init_backward_hook(self)
 
             def flush(bt):
-                bt.repair_bucket_view()
+                # a missing grad is still materialized (zeros in the
+                # bucket view) so that the optimizer sees what it did
+                # before; a live one stays put where nothing reads the
+                # bucket
+                if not bt.bucket_unread or bt.tensor() is None:
+                    bt.repair_bucket_view()
                 backward_hook(bt.name, bt.proxy)
 
             self.bagua_backend.flush_unready(flush)

@@ -46,6 +46,10 @@ class BaguaTensor:
         self.ready_event: Optional[torch.cuda.Event] = None
         self.bucket = None  # back-pointer set by BaguaBucket
         self._bucket_view: Optional[torch.Tensor] = None
+        # set by the backend when buckets are registered: nothing reads
+        # this tensor's bucket (every op on it is an identity at world
+        # size 1), so the effective tensor need not be re-pinned into it
+        self.bucket_unread = False
 
     # ------------------------------------------------------------------
     def tensor(self) -> torch.Tensor:

@@ -101,10 +101,35 @@ def main():
     gbs, us = bench(lambda: lib.fused_sgd_mixed_step(
         pb, gb, master, mm, 0.01, 0.9, 0.0, 1e-4, False, True), 20 * n)
     results.append(("fused_sgd_mixed", "bf16", gbs, us))
+    del pb, gb, master, mm
 
-    print("%-20s %-5s %10s %10s" % ("kernel", "dtype", "GB/s", "us"))
+    # the same step at VGG16's size, flat and through the segmented entry
+    # point with VGG16's 32 gradient tensors, each its own allocation as
+    # autograd leaves them. Same 20 B per parameter either way.
+    from bagua_amd.models import vgg16
+
+    with torch.device("meta"):
+        numels = [q.numel() for q in vgg16(num_classes=1000).parameters()]
+    offsets = [0]
+    for k in numels:
+        offsets.append(offsets[-1] + k)
+    nv = offsets[-1]
+    pb = torch.randn(nv, device="cuda", dtype=torch.bfloat16)
+    gb = torch.randn(nv, device="cuda", dtype=torch.bfloat16)
+    master = pb.float()
+    mm = torch.zeros(nv, device="cuda")
+    gbs, us = bench(lambda: lib.fused_sgd_mixed_step(
+        pb, gb, master, mm, 0.01, 0.9, 0.0, 1e-4, False, True), 20 * nv)
+    results.append(("fused_sgd_mixed@vgg", "bf16", gbs, us))
+    grads = [gb[a:b].clone() for a, b in zip(offsets, offsets[1:])]
+    gbs, us = bench(lambda: lib.fused_sgd_mixed_step_segments(
+        pb, grads, offsets, master, mm, 0.01, 0.9, 0.0, 1e-4, False, True),
+        20 * nv)
+    results.append(("fused_sgd_mixed_segments", "bf16", gbs, us))
+
+    print("%-24s %-5s %10s %10s" % ("kernel", "dtype", "GB/s", "us"))
     for name, dt, gbs, us in results:
-        print("%-20s %-5s %10.0f %10.1f" % (name, dt, gbs, us))
+        print("%-24s %-5s %10.0f %10.1f" % (name, dt, gbs, us))
 
 
 if __name__ == "__main__":
