@@ -108,6 +108,23 @@ void bagua_moe_row_dot_launch(int dtype, const void* g, const void* eo,
                               size_t R, int M, hipStream_t stream);
 }
 
+// epilogue_kernels.hip launchers
+extern "C" {
+size_t bagua_epi_partial_rows(int dtype, size_t work_rows, int C);
+void bagua_epi_bias_relu_launch(int dtype, void* x, const void* bias,
+                                size_t rows, int C, hipStream_t stream);
+void bagua_epi_bias_relu_pool_launch(int dtype, void* x, const void* bias,
+                                     void* p, size_t orows, int Wo, int C,
+                                     hipStream_t stream);
+void bagua_epi_relu_bwd_launch(int dtype, const void* g, const void* y,
+                               void* dx, float* partial, void* db,
+                               size_t rows, int C, hipStream_t stream);
+void bagua_epi_pool_relu_bwd_launch(int dtype, const void* g, const void* y,
+                                    void* dx, float* partial, void* db,
+                                    size_t orows, int Wo, int C,
+                                    hipStream_t stream);
+}
+
 #define HIP_CHECK(cmd)                                                    \
   do {                                                                    \
     hipError_t e = (cmd);                                                 \
@@ -1246,6 +1263,125 @@ static void moe_row_dot(at::Tensor g, at::Tensor eo, at::Tensor dest,
                            current_stream());
 }
 
+// ---------------------------------------------------------------------------
+// convolution epilogue (epilogue_kernels.hip): channels-last (N, C, H, W)
+// tensors, seen by the kernels as [N*H*W, C]
+// ---------------------------------------------------------------------------
+
+// full-size activation of the stage; returns its row count N*H*W
+static int64_t check_epi_act(const at::Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda(), what, " must be a GPU tensor");
+  TORCH_CHECK(t.dim() == 4 &&
+                  t.is_contiguous(at::MemoryFormat::ChannelsLast),
+              what, " must be 4-d and channels-last contiguous");
+  const int64_t vec = 16 / (int64_t)t.element_size();
+  const int64_t C = t.size(1);
+  TORCH_CHECK(C > 0 && C % vec == 0 && C / vec <= 256, what,
+              ": C must be a multiple of ", vec, " and at most ", 256 * vec);
+  TORCH_CHECK(((uintptr_t)t.data_ptr() & 15u) == 0, what,
+              " must be 16-byte aligned");
+  const int64_t rows = t.size(0) * t.size(2) * t.size(3);
+  TORCH_CHECK(rows < kInt31, what, ": N*H*W must be below 2^31");
+  return rows;
+}
+
+static void check_epi_like(const at::Tensor& t, const at::Tensor& ref,
+                           const char* what) {
+  check_epi_act(t, what);
+  TORCH_CHECK(t.sizes() == ref.sizes() &&
+                  t.scalar_type() == ref.scalar_type() &&
+                  t.device() == ref.device(),
+              what, ": shape, dtype or device mismatch");
+}
+
+static void check_epi_bias(const at::Tensor& b, const at::Tensor& act,
+                           const char* what) {
+  check_device_contig(b);
+  TORCH_CHECK(b.dim() == 1 && b.size(0) == act.size(1) &&
+                  b.scalar_type() == act.scalar_type() &&
+                  b.device() == act.device(),
+              what, " must be 1-d of C elements, in the activation's dtype "
+              "and on its device");
+}
+
+// pooled companion of the full-size activation y
+static void check_epi_pooled(const at::Tensor& p, const at::Tensor& y,
+                             const char* what) {
+  TORCH_CHECK(y.size(2) % 2 == 0 && y.size(3) % 2 == 0,
+              "pooling needs even H and W");
+  check_epi_act(p, what);
+  TORCH_CHECK(p.size(0) == y.size(0) && p.size(1) == y.size(1) &&
+                  p.size(2) == y.size(2) / 2 && p.size(3) == y.size(3) / 2 &&
+                  p.scalar_type() == y.scalar_type() &&
+                  p.device() == y.device(),
+              what, " must be (N, C, H/2, W/2) in the activation's dtype");
+}
+
+// x = relu(x + bias), in place
+static void conv_bias_relu_(at::Tensor x, at::Tensor bias) {
+  const int64_t rows = check_epi_act(x, "x");
+  check_epi_bias(bias, x, "bias");
+  bagua_epi_bias_relu_launch(kernel_dtype(x), x.data_ptr(), bias.data_ptr(),
+                             (size_t)rows, (int)x.size(1), current_stream());
+}
+
+// the same, and p = max_pool2d(x, 2, 2)
+static void conv_bias_relu_pool_(at::Tensor x, at::Tensor bias,
+                                 at::Tensor p) {
+  check_epi_act(x, "x");
+  check_epi_bias(bias, x, "bias");
+  check_epi_pooled(p, x, "p");
+  bagua_epi_bias_relu_pool_launch(
+      kernel_dtype(x), x.data_ptr(), bias.data_ptr(), p.data_ptr(),
+      (size_t)(p.size(0) * p.size(2) * p.size(3)), (int)p.size(3),
+      (int)x.size(1), current_stream());
+}
+
+// f32 [blocks, C] scratch of the bias-gradient reduction; from torch's
+// allocator, so a captured graph keeps it
+static at::Tensor epi_partial(const at::Tensor& y, int64_t work_rows) {
+  const int64_t blocks = (int64_t)bagua_epi_partial_rows(
+      kernel_dtype(y), (size_t)work_rows, (int)y.size(1));
+  return at::empty({blocks, y.size(1)}, y.options().dtype(at::kFloat));
+}
+
+// dx = y <= 0 ? 0 : g; db = sum of dx over N, H, W when given
+static void conv_relu_bwd(at::Tensor g, at::Tensor y, at::Tensor dx,
+                          std::optional<at::Tensor> db) {
+  const int64_t rows = check_epi_act(y, "y");
+  check_epi_like(g, y, "g");
+  check_epi_like(dx, y, "dx");
+  at::Tensor partial;
+  if (db.has_value()) {
+    check_epi_bias(*db, y, "db");
+    partial = epi_partial(y, rows);
+  }
+  bagua_epi_relu_bwd_launch(
+      kernel_dtype(y), g.data_ptr(), y.data_ptr(), dx.data_ptr(),
+      db.has_value() ? (float*)partial.data_ptr() : nullptr,
+      db.has_value() ? db->data_ptr() : nullptr, (size_t)rows,
+      (int)y.size(1), current_stream());
+}
+
+// g at pooled size: the gradient goes to each window's winner in y
+static void conv_pool_relu_bwd(at::Tensor g, at::Tensor y, at::Tensor dx,
+                               std::optional<at::Tensor> db) {
+  check_epi_act(y, "y");
+  check_epi_pooled(g, y, "g");
+  check_epi_like(dx, y, "dx");
+  const int64_t orows = g.size(0) * g.size(2) * g.size(3);
+  at::Tensor partial;
+  if (db.has_value()) {
+    check_epi_bias(*db, y, "db");
+    partial = epi_partial(y, orows);
+  }
+  bagua_epi_pool_relu_bwd_launch(
+      kernel_dtype(y), g.data_ptr(), y.data_ptr(), dx.data_ptr(),
+      db.has_value() ? (float*)partial.data_ptr() : nullptr,
+      db.has_value() ? db->data_ptr() : nullptr, (size_t)orows,
+      (int)g.size(3), (int)y.size(1), current_stream());
+}
+
 static py::bytes nccl_unique_id() {
   ncclUniqueId id;
   NCCL_CHECK(ncclGetUniqueId(&id));
@@ -1544,4 +1680,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_combine_rows", &moe_combine_rows, py::arg("eo"),
         py::arg("dest"), py::arg("out"), py::arg("w") = py::none());
   m.def("moe_row_dot", &moe_row_dot);
+  m.def("conv_bias_relu_", &conv_bias_relu_, py::arg("x"), py::arg("bias"));
+  m.def("conv_bias_relu_pool_", &conv_bias_relu_pool_, py::arg("x"),
+        py::arg("bias"), py::arg("p"));
+  m.def("conv_relu_bwd", &conv_relu_bwd, py::arg("g"), py::arg("y"),
+        py::arg("dx"), py::arg("db") = py::none());
+  m.def("conv_pool_relu_bwd", &conv_pool_relu_bwd, py::arg("g"),
+        py::arg("y"), py::arg("dx"), py::arg("db") = py::none());
 }
