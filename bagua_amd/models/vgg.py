@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops import conv_epilogue
+from ..ops import conv_epilogue, first_conv
 
 _CFGS = {
     "A": [64, "M", 128, "M", 256, 256, "M", 512, 512, "M", 512, 512, "M"],
@@ -69,6 +69,13 @@ class VGG(nn.Module):
         while i < len(mods):
             m = mods[i]
             step = _fusable(mods, i)
+            if (step == 2 and not self.torch_bias_grad
+                    and first_conv.eligible(x, m)):
+                # the image's own stage: convolution, bias and ReLU in one
+                # kernel each way (ops/first_conv.py)
+                x = first_conv.first_conv_bias_relu(x, m.weight, m.bias)
+                i += 2
+                continue
             if step:
                 pool = step == 3 and conv_epilogue.conv_eligible(x, m, True)
                 if pool or conv_epilogue.conv_eligible(x, m, False):

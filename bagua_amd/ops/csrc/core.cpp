@@ -26,6 +26,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 // kernels.hip launchers
@@ -123,6 +124,20 @@ void bagua_epi_pool_relu_bwd_launch(int dtype, const void* g, const void* y,
                                     void* dx, float* partial, void* db,
                                     size_t orows, int Wo, int C,
                                     hipStream_t stream);
+}
+
+// first_conv_kernels.hip launchers
+extern "C" {
+size_t bagua_first_conv_partial_rows(int N, int H, int W);
+size_t bagua_first_conv_partial_cols();
+void bagua_first_conv_fwd_launch(const void* x, const void* w,
+                                 const long* wstride, const void* bias,
+                                 void* y, int N, int H, int W,
+                                 hipStream_t stream);
+void bagua_first_conv_bwd_launch(const void* g, const void* y, const void* x,
+                                 float* partial, void* dw,
+                                 const long* wstride, void* db, int N, int H,
+                                 int W, hipStream_t stream);
 }
 
 #define HIP_CHECK(cmd)                                                    \
@@ -1382,6 +1397,93 @@ static void conv_pool_relu_bwd(at::Tensor g, at::Tensor y, at::Tensor dx,
       (int)g.size(3), (int)y.size(1), current_stream());
 }
 
+// ---------------------------------------------------------------------------
+// first convolution (first_conv_kernels.hip): Conv2d(3, 64, 3, padding=1)
+// with bias and ReLU on a channels-last bf16 image
+// ---------------------------------------------------------------------------
+
+// the image; returns its pixel count N*H*W
+static int64_t check_first_conv_x(const at::Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), "x must be a GPU tensor");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "x must be bf16");
+  TORCH_CHECK(x.dim() == 4 && x.size(1) == 3 &&
+                  x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "x must be (N, 3, H, W) and channels-last contiguous");
+  const int64_t rows = x.size(0) * x.size(2) * x.size(3);
+  TORCH_CHECK(rows > 0 && rows < kInt31,
+              "x: N*H*W must be at least 1 and below 2^31");
+  return rows;
+}
+
+// the (64, 3, 3, 3) weight or its gradient: dense, in either memory format
+static void check_first_conv_weight(const at::Tensor& w,
+                                    const at::Tensor& x, const char* what) {
+  TORCH_CHECK(w.is_cuda() && w.device() == x.device() &&
+                  w.scalar_type() == at::kBFloat16,
+              what, " must be bf16 on x's device");
+  TORCH_CHECK(w.dim() == 4 && w.size(0) == 64 && w.size(1) == 3 &&
+                  w.size(2) == 3 && w.size(3) == 3,
+              what, " must be (64, 3, 3, 3)");
+  TORCH_CHECK(w.is_contiguous() ||
+                  w.is_contiguous(at::MemoryFormat::ChannelsLast),
+              what, " must be contiguous or channels-last contiguous");
+}
+
+// the 64-channel activation of the stage, or its gradient
+static void check_first_conv_act(const at::Tensor& t, const at::Tensor& x,
+                                 const char* what) {
+  check_epi_act(t, what);
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.device() == x.device() &&
+                  t.size(0) == x.size(0) && t.size(1) == 64 &&
+                  t.size(2) == x.size(2) && t.size(3) == x.size(3),
+              what, " must be (N, 64, H, W) bf16 on x's device");
+}
+
+// y = relu(conv2d(x, weight, padding=1) + bias)
+static at::Tensor first_conv_bias_relu(at::Tensor x, at::Tensor weight,
+                                       at::Tensor bias) {
+  check_first_conv_x(x);
+  check_first_conv_weight(weight, x, "weight");
+  at::Tensor y = at::empty({x.size(0), 64, x.size(2), x.size(3)},
+                           x.options().memory_format(
+                               at::MemoryFormat::ChannelsLast));
+  check_first_conv_act(y, x, "y");
+  check_epi_bias(bias, y, "bias");
+  const long ws[4] = {(long)weight.stride(0), (long)weight.stride(1),
+                      (long)weight.stride(2), (long)weight.stride(3)};
+  bagua_first_conv_fwd_launch(x.data_ptr(), weight.data_ptr(), ws,
+                              bias.data_ptr(), y.data_ptr(), (int)x.size(0),
+                              (int)x.size(2), (int)x.size(3),
+                              current_stream());
+  return y;
+}
+
+// dx = y <= 0 ? 0 : g is formed on the fly; returns the weight gradient, in
+// weight_like's strides, and the bias gradient
+static std::tuple<at::Tensor, at::Tensor> first_conv_bias_relu_bwd(
+    at::Tensor g, at::Tensor y, at::Tensor x, at::Tensor weight_like) {
+  check_first_conv_x(x);
+  check_first_conv_weight(weight_like, x, "weight_like");
+  check_first_conv_act(y, x, "y");
+  check_first_conv_act(g, x, "g");
+  at::Tensor dw = at::empty_strided(weight_like.sizes(),
+                                    weight_like.strides(), y.options());
+  at::Tensor db = at::empty({64}, y.options());
+  const int N = (int)x.size(0), H = (int)x.size(2), W = (int)x.size(3);
+  // f32 [blocks, 64 * 28] partial sums; from torch's allocator, so a
+  // captured graph keeps it
+  at::Tensor partial = at::empty(
+      {(int64_t)bagua_first_conv_partial_rows(N, H, W),
+       (int64_t)bagua_first_conv_partial_cols()},
+      y.options().dtype(at::kFloat));
+  const long ws[4] = {(long)dw.stride(0), (long)dw.stride(1),
+                      (long)dw.stride(2), (long)dw.stride(3)};
+  bagua_first_conv_bwd_launch(g.data_ptr(), y.data_ptr(), x.data_ptr(),
+                              (float*)partial.data_ptr(), dw.data_ptr(), ws,
+                              db.data_ptr(), N, H, W, current_stream());
+  return std::make_tuple(dw, db);
+}
+
 static py::bytes nccl_unique_id() {
   ncclUniqueId id;
   NCCL_CHECK(ncclGetUniqueId(&id));
@@ -1687,4 +1789,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dx"), py::arg("db") = py::none());
   m.def("conv_pool_relu_bwd", &conv_pool_relu_bwd, py::arg("g"),
         py::arg("y"), py::arg("dx"), py::arg("db") = py::none());
+  m.def("first_conv_bias_relu", &first_conv_bias_relu, py::arg("x"),
+        py::arg("weight"), py::arg("bias"));
+  m.def("first_conv_bias_relu_bwd", &first_conv_bias_relu_bwd, py::arg("g"),
+        py::arg("y"), py::arg("x"), py::arg("weight_like"));
 }

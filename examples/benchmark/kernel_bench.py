@@ -127,6 +127,27 @@ def main():
         20 * nv)
     results.append(("fused_sgd_mixed_segments", "bf16", gbs, us))
 
+    del pb, gb, master, mm, grads
+
+    # VGG16's first stage at the flagship's size, 32 x 224 x 224:
+    # Conv2d(3, 64, 3, padding=1) + bias + ReLU as one kernel each way.
+    # bytes: forward reads x and writes y; backward reads g, y and x
+    # (weights, bias and the f32 partial sums are noise next to those)
+    cl = dict(memory_format=torch.channels_last)
+    xi = torch.randn(32, 3, 224, 224, device="cuda",
+                     dtype=torch.bfloat16).contiguous(**cl)
+    wt = torch.randn(64, 3, 3, 3, device="cuda", dtype=torch.bfloat16) * 0.2
+    bs = torch.randn(64, device="cuda", dtype=torch.bfloat16)
+    yo = lib.first_conv_bias_relu(xi, wt, bs)
+    go = torch.randn_like(yo)
+    es = 2
+    gbs, us = bench(lambda: lib.first_conv_bias_relu(xi, wt, bs),
+                    (xi.numel() + yo.numel()) * es)
+    results.append(("first_conv_fwd@vgg", "bf16", gbs, us))
+    gbs, us = bench(lambda: lib.first_conv_bias_relu_bwd(go, yo, xi, wt),
+                    (2 * yo.numel() + xi.numel()) * es)
+    results.append(("first_conv_bwd@vgg", "bf16", gbs, us))
+
     print("%-24s %-5s %10s %10s" % ("kernel", "dtype", "GB/s", "us"))
     for name, dt, gbs, us in results:
         print("%-24s %-5s %10.0f %10.1f" % (name, dt, gbs, us))

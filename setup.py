@@ -20,6 +20,7 @@ ext = cpp_extension.CUDAExtension(
         "bagua_amd/ops/csrc/kernels.hip",
         "bagua_amd/ops/csrc/moe_kernels.hip",
         "bagua_amd/ops/csrc/epilogue_kernels.hip",
+        "bagua_amd/ops/csrc/first_conv_kernels.hip",
     ],
     include_dirs=[os.path.join(ROCM_HOME, "include")],
     libraries=["rccl"],
