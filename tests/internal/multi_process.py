@@ -4,7 +4,10 @@ Mirrors the reference's test pattern (tests/internal/multi_process.py:9-53):
 each worker gets a hand-rolled env (WORLD_SIZE/RANK/LOCAL_RANK/MASTER_*)
 on a fresh port, runs the target function, and ships results back through
 a multiprocessing queue. On the CPU CI this exercises the gloo path; the
-same harness with cuda devices runs under ``-m gpu`` on the MI355X box.
+same harness with cuda devices runs under ``-m gpu`` where there is one
+GPU per worker. On a single GPU the bucket protocols run at world sizes
+above 1 in the simulated world of tests/internal/sim_world.py instead
+(threads in one process, tests/test_gpu_sim_world.py).
 """
 
 import multiprocessing as mp
