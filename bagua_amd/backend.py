@@ -142,6 +142,8 @@ class BaguaBackend:
             if p2p.enabled() and (op.compression is not None
                                   or op.scattergather):
                 return False
+            if op.momentum_beta1 is not None:  # the momentum kernel is f32
+                return b._flat.dtype == torch.float32
             return b._flat.dtype in (torch.float32, torch.float16,
                                      torch.bfloat16)
 
@@ -233,7 +235,7 @@ class BaguaBackend:
         for op in bucket.ops:
             if not isinstance(op, CentralizedSyncOp):
                 return False
-            if op.compression is not None:
+            if op.compression is not None or op.momentum_beta1 is not None:
                 return False
             group = op.group or self.group
             if len(group.ranks) != 1:
@@ -255,7 +257,16 @@ class BaguaBackend:
             for t in bucket.tensors:
                 if t.ready_event is not None:
                     events.append(t.ready_event.cuda_event)
-            self._native_exec.execute(bucket._native_idx, events)
+            beta1 = bucket.ops[0].momentum_beta1
+            if beta1 is None:
+                self._native_exec.execute(bucket._native_idx, events)
+            else:
+                # contiguous gradients of the bucket's dtype (what
+                # FusedQAdamOptimizer's parameters get); others are refused
+                self._native_exec.execute_momentum(
+                    bucket._native_idx, events,
+                    [t.proxy.grad for t in bucket.tensors],
+                    bucket.segment_offsets(), beta1)
             for t in bucket.tensors:
                 if t.ready_event is not None:
                     self.event_pool.put(t.ready_event)

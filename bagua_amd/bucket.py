@@ -43,6 +43,9 @@ class CentralizedSyncOp:
     scattergather: bool = False
     compression: Optional[str] = None  # None | "MinMaxUInt8"
     group: object = None  # BaguaProcessGroup
+    # QAdam after warmup: the bucket holds the first moment, and before the
+    # sync it takes m = beta1 * m + (1 - beta1) * proxy.grad per tensor
+    momentum_beta1: Optional[float] = None
 
 
 @dataclass
@@ -218,11 +221,21 @@ class BaguaBucket:
         scattergather: bool = False,
         compression: Optional[str] = None,
         group=None,
+        momentum_beta1: Optional[float] = None,
     ):
         self.ops.append(CentralizedSyncOp(
             hierarchical=hierarchical, average=average,
-            scattergather=scattergather, compression=compression, group=group))
+            scattergather=scattergather, compression=compression, group=group,
+            momentum_beta1=momentum_beta1))
         return self
+
+    def segment_offsets(self) -> List[int]:
+        """Where each tensor begins in the fused buffer, plus the end of
+        the last one (the padding follows)."""
+        offsets = [0]
+        for t in self.tensors:
+            offsets.append(offsets[-1] + t.numel())
+        return offsets
 
     def append_decentralized_synchronous_op(
         self,

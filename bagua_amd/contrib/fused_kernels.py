@@ -20,6 +20,37 @@ import torch
 from ..ops import native
 
 
+def flatten_params(params):
+    """Re-point ``params`` into one flat buffer; the record the segmented
+    steps work on (None for an empty list)."""
+    if not params:
+        return None
+    total = sum(p.numel() for p in params)
+    p0 = params[0]
+    flat_w = torch.zeros(total, dtype=p0.dtype, device=p0.device)
+    offsets = [0]
+    for p in params:
+        w_view = flat_w.narrow(0, offsets[-1], p.numel()).view_as(p)
+        w_view.copy_(p.detach())
+        p.data = w_view
+        offsets.append(offsets[-1] + p.numel())
+    return {"params": params, "flat_w": flat_w, "offsets": offsets}
+
+
+def segment_grads(rec):
+    """The live grads, one per segment, as the kernels take them: None
+    stays None (a zero gradient); a grad of another dtype or layout is
+    made conforming for its segment only."""
+    dtype = rec["flat_w"].dtype
+    grads = []
+    for p in rec["params"]:
+        g = p.grad
+        if g is not None and (g.dtype != dtype or not g.is_contiguous()):
+            g = g.detach().to(dtype).contiguous()
+        grads.append(g)
+    return grads
+
+
 class _FlatGroupOptimizer(torch.optim.Optimizer):
     """Flattens each param group's weights (and state) once. Gradients
     are not flattened: the GPU kernels read each ``p.grad`` where it lives
@@ -27,34 +58,10 @@ class _FlatGroupOptimizer(torch.optim.Optimizer):
     segmented entry points of the extension."""
 
     def _flatten_group(self, group):
-        params = [p for p in group["params"] if p.requires_grad]
-        if not params:
-            return None
-        total = sum(p.numel() for p in params)
-        p0 = params[0]
-        flat_w = torch.zeros(total, dtype=p0.dtype, device=p0.device)
-        offsets = [0]
-        for p in params:
-            w_view = flat_w.narrow(0, offsets[-1], p.numel()).view_as(p)
-            w_view.copy_(p.detach())
-            p.data = w_view
-            offsets.append(offsets[-1] + p.numel())
-        return {"params": params, "flat_w": flat_w, "offsets": offsets}
+        return flatten_params(
+            [p for p in group["params"] if p.requires_grad])
 
-    @staticmethod
-    def _segment_grads(rec):
-        """The live grads, one per segment, as the kernels take them:
-        None stays None (a zero gradient); a grad of another dtype or
-        layout is made conforming for its segment only."""
-        dtype = rec["flat_w"].dtype
-        grads = []
-        for p in rec["params"]:
-            g = p.grad
-            if g is not None and (g.dtype != dtype
-                                  or not g.is_contiguous()):
-                g = g.detach().to(dtype).contiguous()
-            grads.append(g)
-        return grads
+    _segment_grads = staticmethod(segment_grads)
 
     @staticmethod
     def _gathered_grad(rec):

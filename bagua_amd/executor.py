@@ -99,6 +99,12 @@ def _exec_centralized(op: CentralizedSyncOp, bucket: BaguaBucket,
                       group: BaguaProcessGroup):
     with bucket.comm_view() as flat:
         ctx = _HierCtx(group, op.hierarchical)
+        if op.momentum_beta1 is not None:
+            # ahead of the intra-node reduce: every rank contributes its
+            # updated momentum
+            ops.qadam_momentum_update(
+                flat, [t.proxy.grad for t in bucket.tensors],
+                bucket.segment_offsets(), op.momentum_beta1)
         ctx.pre(flat, average=op.average)
         if ctx.run_inner():
             comm = ctx.comm()

@@ -103,6 +103,42 @@ def compress_chunked(flat: torch.Tensor, num_chunks: int,
     return quant.compress_chunked(flat, num_chunks, target_chunk, out)
 
 
+def qadam_momentum_update(flat_m: torch.Tensor, grads, offsets,
+                          beta1: float):
+    """QAdam's momentum update on a bucket, the gradients read in place:
+    ``flat_m = beta1 * flat_m + (1 - beta1) * grad``. ``grads[k]`` covers
+    ``flat_m[offsets[k]:offsets[k + 1]]``; ``None``, and the padding behind
+    ``offsets[-1]``, are zero gradients."""
+    if flat_m.is_cuda and native.available():
+        native.lib().qadam_momentum_compress_chunked(
+            flat_m, list(grads), list(offsets), beta1, None, 1)
+        return
+    for k, g in enumerate(grads):
+        seg = flat_m[offsets[k]:offsets[k + 1]].mul_(beta1)
+        if g is not None:
+            seg.add_(g.detach().reshape(-1), alpha=1 - beta1)
+    flat_m[offsets[-1]:].mul_(beta1)
+
+
+def qadam_momentum_compress_chunked(flat_m: torch.Tensor, grads, offsets,
+                                    beta1: float, num_chunks: int,
+                                    out: torch.Tensor = None
+                                    ) -> torch.Tensor:
+    """:func:`qadam_momentum_update`, then :func:`compress_chunked` of all
+    chunks of the new momentum — on the GPU in one pass over it for both
+    the update and the min/max (f32 buckets only)."""
+    if flat_m.is_cuda and native.available():
+        if out is None:
+            out = torch.empty(
+                compressed_buffer_numel(flat_m.numel(), num_chunks),
+                dtype=torch.uint8, device=flat_m.device)
+        native.lib().qadam_momentum_compress_chunked(
+            flat_m, list(grads), list(offsets), beta1, out, num_chunks)
+        return out
+    qadam_momentum_update(flat_m, grads, offsets, beta1)
+    return quant.compress_chunked(flat_m, num_chunks, -1, out)
+
+
 def dequant_reduce(buf: torch.Tensor, flat: torch.Tensor, num_chunks: int,
                    target_chunk: int, average: bool):
     """Fused: flat[target_chunk] = reduce over the dequantized wire

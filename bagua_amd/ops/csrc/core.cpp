@@ -87,6 +87,16 @@ void bagua_fused_adam_segments_launch(
     float weight_decay, int adamw, float bc1, float bc2,
     const void* const* grads, const size_t* begins, const size_t* numels,
     size_t count, hipStream_t stream);
+size_t bagua_qadam_momentum_max_segments();
+void bagua_qadam_momentum_compress_launch(
+    float* m, const void* const* grads, const size_t* begins,
+    const size_t* numels, size_t count, float beta1, float one_minus_beta1,
+    uint8_t* out, uint32_t* scratch, uint32_t* partials, size_t chunk,
+    size_t chunk_stride, int num_chunks, hipStream_t stream);
+void bagua_qadam_frozen_segments_launch(
+    float* p, const float* v, float lr, float eps, float bc1, float bc2,
+    const void* const* moms, const size_t* begins, const size_t* numels,
+    size_t count, hipStream_t stream);
 }
 
 // moe_kernels.hip launchers
@@ -557,8 +567,29 @@ class BucketExecutor {
     return (int)buckets_.size() - 1;
   }
 
+  // QAdam's momentum update m = beta1 * m + (1 - beta1) * grad on the
+  // bucket, ahead of its sync: the segments of the bucket's tensors
+  struct Momentum {
+    std::vector<const void*> grads;
+    std::vector<size_t> begins, numels;
+    float beta1, one_minus_beta1;
+  };
+
   void execute(int idx, const std::vector<uintptr_t>& ready_events) {
     py::gil_scoped_release nogil;
+    run(idx, ready_events, nullptr);
+  }
+
+  // execute() with the momentum update first: fused into the first
+  // compress on one node, on its own ahead of the intra-node reduce
+  // otherwise. The gradients were produced on the compute stream; the
+  // tensors' ready events order them, as they order the bucket.
+  void execute_momentum(int idx, const std::vector<uintptr_t>& ready_events,
+                        std::vector<std::optional<at::Tensor>> grads,
+                        std::vector<int64_t> offsets, double beta1);
+
+  void run(int idx, const std::vector<uintptr_t>& ready_events,
+           const Momentum* mom) {
     Bucket& b = buckets_.at(idx);
     for (uintptr_t ev : ready_events)
       HIP_CHECK(hipStreamWaitEvent(stream_, (hipEvent_t)ev, 0));
@@ -567,12 +598,16 @@ class BucketExecutor {
                       intra_->nranks() < global_->nranks();
     Communicator* comm = multi_node ? inter_.get() : global_.get();
 
+    if (mom != nullptr && (multi_node || !b.compressed)) {
+      update_momentum(b, *mom, 1, nullptr, nullptr, nullptr, 0);
+      mom = nullptr;
+    }
     if (multi_node)
       intra_->reduce_inplace(b.flat, 0, b.average ? 10 : 0);
     if (!multi_node || intra_->rank() == 0) {
       TORCH_CHECK(comm != nullptr, "leader rank missing inter communicator");
       if (b.compressed)
-        run_compressed(b, comm);
+        run_compressed(b, comm, mom);
       else if (b.scattergather)
         run_scattergather(b, comm);
       else
@@ -628,7 +663,17 @@ class BucketExecutor {
     comm->allgather_inplace(b.flat);
   }
 
-  void run_compressed(Bucket& b, Communicator* comm) {
+  void update_momentum(Bucket& b, const Momentum& mom, int num_chunks,
+                       uint8_t* wire, uint32_t* scratch, uint32_t* partials,
+                       int64_t stride) {
+    bagua_qadam_momentum_compress_launch(
+        (float*)b.flat.data_ptr(), mom.grads.data(), mom.begins.data(),
+        mom.numels.data(), mom.grads.size(), mom.beta1, mom.one_minus_beta1,
+        wire, scratch, partials, b.flat.numel() / num_chunks, stride,
+        num_chunks, stream_);
+  }
+
+  void run_compressed(Bucket& b, Communicator* comm, const Momentum* mom) {
     // ByteGrad wire protocol (reference:
     // comm_ops/centralized_low_precision_synchronous.rs:16-74)
     int n = comm->nranks();
@@ -640,8 +685,11 @@ class BucketExecutor {
     auto* scratch = (uint32_t*)b.scratch.data_ptr();
     auto* partials = (uint32_t*)b.partials.data_ptr();
 
-    bagua_compress_launch(dt, b.flat.data_ptr(), wire, scratch, partials,
-                          chunk, stride, n, 0, n, stream_);
+    if (mom != nullptr)
+      update_momentum(b, *mom, n, wire, scratch, partials, stride);
+    else
+      bagua_compress_launch(dt, b.flat.data_ptr(), wire, scratch, partials,
+                            chunk, stride, n, 0, n, stream_);
     comm->alltoall(b.wire, b.wire_tmp);
     std::swap(b.wire, b.wire_tmp);
     wire = (uint8_t*)b.wire.data_ptr();
@@ -1052,11 +1100,14 @@ struct GradSegments {
 
 static GradSegments check_segments(
     const at::Tensor& p, const std::vector<std::optional<at::Tensor>>& grads,
-    const std::vector<int64_t>& offsets) {
+    const std::vector<int64_t>& offsets, bool padded = false) {
   check_device_contig(p);
   TORCH_CHECK(offsets.size() == grads.size() + 1,
               "need len(grads) + 1 offsets");
-  TORCH_CHECK(offsets.front() == 0 && offsets.back() == p.numel(),
+  // padded: p may go on behind the last segment (a bucket's tail padding)
+  TORCH_CHECK(offsets.front() == 0 &&
+                  (padded ? offsets.back() <= p.numel()
+                          : offsets.back() == p.numel()),
               "segments must tile [0, numel)");
   GradSegments s;
   for (size_t k = 0; k < grads.size(); ++k) {
@@ -1143,6 +1194,83 @@ static void fused_adam_step_segments(
       (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
       (float)weight_decay, adamw ? 1 : 0, bc1, bc2, s.grads.data(),
       s.begins.data(), s.numels.data(), s.grads.size(), current_stream());
+}
+
+// QAdam's step once the second moment is frozen: w and v flat, the
+// momentum read where it lives (moms[k] covers [offsets[k], offsets[k+1])).
+static void qadam_frozen_step_segments(
+    at::Tensor p, std::vector<std::optional<at::Tensor>> moms,
+    std::vector<int64_t> offsets, at::Tensor v, int64_t step, double lr,
+    double beta1, double beta2, double eps) {
+  TORCH_CHECK(p.scalar_type() == at::kFloat, "fused QAdam needs f32 weights");
+  const GradSegments s = check_segments(p, moms, offsets);
+  const float* vp = check_flat_state(v, p, true, "exp_avg_sq");
+  float bc1 = (float)(1.0 - std::pow(beta1, (double)step));
+  float bc2 = (float)(1.0 - std::pow(beta2, (double)step));
+  bagua_qadam_frozen_segments_launch(
+      (float*)p.data_ptr(), vp, (float)lr, (float)eps, bc1, bc2,
+      s.grads.data(), s.begins.data(), s.numels.data(), s.grads.size(),
+      current_stream());
+}
+
+static GradSegments check_momentum_segments(
+    const at::Tensor& flat_m,
+    const std::vector<std::optional<at::Tensor>>& grads,
+    const std::vector<int64_t>& offsets) {
+  TORCH_CHECK(flat_m.scalar_type() == at::kFloat,
+              "the QAdam momentum kernel needs an f32 bucket");
+  TORCH_CHECK(flat_m.numel() > 0, "empty momentum bucket");
+  GradSegments s = check_segments(flat_m, grads, offsets, /*padded=*/true);
+  TORCH_CHECK(s.grads.size() < bagua_qadam_momentum_max_segments(),
+              "too many tensors in one bucket");
+  return s;
+}
+
+// flat_m = beta1 * flat_m + (1 - beta1) * grad, the gradients read in place
+// (grads[k] covers [offsets[k], offsets[k+1]), None and what lies behind
+// offsets[-1] are zero gradients); then, with out, the MinMaxUInt8 wire of
+// all num_chunks chunks of the new flat_m, as compress_chunked writes it.
+static void qadam_momentum_compress_chunked(
+    at::Tensor flat_m, std::vector<std::optional<at::Tensor>> grads,
+    std::vector<int64_t> offsets, double beta1,
+    std::optional<at::Tensor> out, int64_t num_chunks) {
+  const GradSegments s = check_momentum_segments(flat_m, grads, offsets);
+  TORCH_CHECK(num_chunks >= 1 && flat_m.numel() % num_chunks == 0,
+              "chunked size mismatch");
+  const int64_t chunk = flat_m.numel() / num_chunks;
+  const int64_t stride = compressed_chunk_stride(chunk);
+  uint8_t* wire = nullptr;
+  at::Tensor scratch, partials;
+  if (out.has_value()) {
+    check_device_contig(*out);
+    TORCH_CHECK(out->scalar_type() == at::kByte &&
+                    out->device() == flat_m.device(),
+                "wire buffer must be uint8 on the bucket's device");
+    TORCH_CHECK(out->numel() >= stride * num_chunks, "wire buffer too small");
+    wire = (uint8_t*)out->data_ptr();
+    scratch = at::empty({2 * num_chunks}, flat_m.options().dtype(at::kInt));
+    partials = at::empty({2 * 512 * num_chunks},
+                         flat_m.options().dtype(at::kInt));
+  }
+  bagua_qadam_momentum_compress_launch(
+      (float*)flat_m.data_ptr(), s.grads.data(), s.begins.data(),
+      s.numels.data(), s.grads.size(), (float)beta1, (float)(1.0 - beta1),
+      wire, wire ? (uint32_t*)scratch.data_ptr() : nullptr,
+      wire ? (uint32_t*)partials.data_ptr() : nullptr, chunk, stride,
+      (int)num_chunks, current_stream());
+}
+
+inline void BucketExecutor::execute_momentum(
+    int idx, const std::vector<uintptr_t>& ready_events,
+    std::vector<std::optional<at::Tensor>> grads,
+    std::vector<int64_t> offsets, double beta1) {
+  GradSegments s = check_momentum_segments(buckets_.at(idx).flat, grads,
+                                           offsets);
+  const Momentum mom{std::move(s.grads), std::move(s.begins),
+                     std::move(s.numels), (float)beta1,
+                     (float)(1.0 - beta1)};
+  py::gil_scoped_release nogil;
+  run(idx, ready_events, &mom);
 }
 
 // ---------------------------------------------------------------------------
@@ -1732,6 +1860,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("inter_comm") = nullptr, py::arg("stream") = 0)
       .def("register_bucket", &BucketExecutor::register_bucket)
       .def("execute", &BucketExecutor::execute)
+      .def("execute_momentum", &BucketExecutor::execute_momentum,
+           py::arg("idx"), py::arg("ready_events"), py::arg("grads"),
+           py::arg("offsets"), py::arg("beta1"))
       .def("wait_pending", &BucketExecutor::wait_pending)
       .def("synchronize", &BucketExecutor::synchronize)
       .def("clear_buckets", &BucketExecutor::clear_buckets);
@@ -1773,6 +1904,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grads"), py::arg("offsets"), py::arg("m"), py::arg("v"),
         py::arg("step"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("weight_decay"), py::arg("adamw"));
+  m.def("qadam_frozen_step_segments", &qadam_frozen_step_segments,
+        py::arg("p"), py::arg("moms"), py::arg("offsets"), py::arg("v"),
+        py::arg("step"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"));
+  m.def("qadam_momentum_compress_chunked", &qadam_momentum_compress_chunked,
+        py::arg("flat_m"), py::arg("grads"), py::arg("offsets"),
+        py::arg("beta1"), py::arg("out"), py::arg("num_chunks"));
   m.def("moe_assign_slots", &moe_assign_slots, py::arg("expert"),
         py::arg("num_experts"), py::arg("capacity"), py::arg("base"),
         py::arg("slot"), py::arg("counts"), py::arg("src"));

@@ -15,6 +15,8 @@ from torch.optim.optimizer import Optimizer
 
 from ...bucket import BaguaBucket
 from ...communication import BaguaProcessGroup
+from ...contrib.fused_kernels import flatten_params, segment_grads
+from ...ops import native
 from ...tensor import BaguaTensor
 from .base import Algorithm, AlgorithmImpl
 
@@ -82,6 +84,108 @@ class QAdamOptimizer(Optimizer):
         return loss
 
 
+class FusedQAdamOptimizer(QAdamOptimizer):
+    """QAdam whose device math is hand-written HIP (f32 parameters only).
+
+    Weights and ``exp_avg_sq`` are flattened once per group; during warmup
+    ``exp_avg`` is flat too and a step is one fused Adam launch per group.
+    After warmup ``exp_avg`` lives in the communication buckets (the
+    algorithm re-points ``state[p]["exp_avg"]`` there), a bucket's momentum
+    update is fused into the min/max pass of its compressed sync, and a
+    step is one launch per group that reads the momentum where it lives.
+    ``state[p]`` keeps ``step``, ``exp_avg`` and ``exp_avg_sq`` per
+    parameter, the tensors as views of the flat state. On CPU, or without
+    the extension, the parent's math runs on those views.
+    """
+
+    def __init__(self, params, lr: float = 1e-3, warmup_steps: int = 100,
+                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0):
+        super().__init__(params, lr=lr, warmup_steps=warmup_steps,
+                         betas=betas, eps=eps, weight_decay=weight_decay)
+        self._flat = []
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.dtype != torch.float32:
+                    raise TypeError(
+                        "FusedQAdamOptimizer supports float32 parameters "
+                        "only, got %s; use QAdamOptimizer" % p.dtype)
+            # every parameter, as the parent's step takes them all
+            rec = flatten_params(list(group["params"]))
+            self._flat.append(rec)
+            if rec is None:
+                continue
+            for name in ("exp_avg", "exp_avg_sq"):
+                rec[name] = torch.zeros_like(rec["flat_w"])
+            for k, p in enumerate(rec["params"]):
+                begin = rec["offsets"][k]
+                self.state[p] = {
+                    "step": 0,
+                    "exp_avg": rec["exp_avg"].narrow(
+                        0, begin, p.numel()).view_as(p),
+                    "exp_avg_sq": rec["exp_avg_sq"].narrow(
+                        0, begin, p.numel()).view_as(p),
+                }
+
+    def _native(self):
+        return native.available() and all(
+            rec is None or rec["flat_w"].is_cuda for rec in self._flat)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if not self._native():
+            return super().step(closure)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = native.lib()
+        for group, rec in zip(self.param_groups, self._flat):
+            if rec is None:
+                continue
+            params = rec["params"]
+            for p in params:
+                self.state[p]["step"] += 1
+            step_id = self.state[params[0]]["step"]
+            beta1, beta2 = group["betas"]
+            if step_id < self.warmup_steps:
+                base = rec["exp_avg"].data_ptr()
+                for k, p in enumerate(params):
+                    if self.state[p]["exp_avg"].data_ptr() \
+                            != base + 4 * rec["offsets"][k]:
+                        raise RuntimeError(
+                            "exp_avg left the flat state before the end "
+                            "of warmup")
+                lib.fused_adam_step_segments(
+                    rec["flat_w"], segment_grads(rec),
+                    rec["offsets"], rec["exp_avg"], rec["exp_avg_sq"],
+                    step_id, group["lr"], beta1, beta2, group["eps"],
+                    group["weight_decay"], False)
+            else:
+                # the moments are frozen (v) or kept by the communication
+                # path (m), at the boundary step too
+                lib.qadam_frozen_step_segments(
+                    rec["flat_w"],
+                    [self.state[p]["exp_avg"] for p in params],
+                    rec["offsets"], rec["exp_avg_sq"], step_id, group["lr"],
+                    beta1, beta2, group["eps"])
+        return loss
+
+    def load_state_dict(self, state_dict):
+        """Copies into the views of the flat state (and of the buckets)
+        instead of replacing them."""
+        views = {p: dict(self.state[p]) for rec in self._flat
+                 if rec is not None for p in rec["params"]}
+        super().load_state_dict(state_dict)
+        for p, old in views.items():
+            new = self.state[p]
+            for name in ("exp_avg", "exp_avg_sq"):
+                if name in new:
+                    old[name].copy_(new[name])
+                new[name] = old[name]
+            new["step"] = int(new.get("step", old["step"]))
+
+
 class QAdamAlgorithmImpl(AlgorithmImpl):
     def __init__(self, process_group: BaguaProcessGroup,
                  q_adam_optimizer: QAdamOptimizer,
@@ -144,6 +248,14 @@ class QAdamAlgorithmImpl(AlgorithmImpl):
         if self.optimizer_step_id < self.warmup_steps:
             bucket.append_centralized_synchronous_op(
                 hierarchical=False, average=True, group=self.process_group)
+        elif isinstance(self.optimizer, FusedQAdamOptimizer):
+            # one op: the momentum update rides on the sync, which keeps
+            # the bucket on the native executor
+            beta1, _ = self.optimizer.param_groups[0]["betas"]
+            bucket.append_centralized_synchronous_op(
+                hierarchical=self.hierarchical, average=True,
+                scattergather=True, compression="MinMaxUInt8",
+                group=self.process_group, momentum_beta1=beta1)
         else:
 
             def calculate_momentum(*args):

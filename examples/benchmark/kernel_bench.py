@@ -129,6 +129,37 @@ def main():
 
     del pb, gb, master, mm, grads
 
+    # QAdam after warmup at VGG16's size, one bucket of 8 chunks, the 32
+    # gradients (momenta) each their own allocation. Momentum + wire: read
+    # m and g, write m (12 B), quantize reads m and writes u8 (5 B); the
+    # unfused pair next to it is minmax + quantize alone (4 + 5 B, it has
+    # no update). Frozen step: read w, v and m, write w (16 B); fused Adam
+    # on the same tensors for scale (28 B).
+    chunks = 8
+    nm = (nv + 32 * chunks - 1) // (32 * chunks) * (32 * chunks)
+    fm = torch.randn(nm, device="cuda") * 0.1
+    gq = [torch.randn(b - a, device="cuda")
+          for a, b in zip(offsets, offsets[1:])]
+    wire = torch.empty(lib.compressed_chunk_stride(nm // chunks) * chunks,
+                       dtype=torch.uint8, device="cuda")
+    gbs, us = bench(lambda: lib.qadam_momentum_compress_chunked(
+        fm, gq, offsets, 0.9, wire, chunks), 17 * nm)
+    results.append(("qadam_momentum_compress@vgg", "f32", gbs, us))
+    gbs, us = bench(lambda: lib.compress_chunked(fm, wire, chunks, -1),
+                    9 * nm)
+    results.append(("  minmax + quantize@vgg", "f32", gbs, us))
+    fw = torch.randn(nv, device="cuda")
+    fv = torch.rand(nv, device="cuda")
+    gbs, us = bench(lambda: lib.qadam_frozen_step_segments(
+        fw, gq, offsets, fv, 200, 1e-3, 0.9, 0.999, 1e-8), 16 * nv)
+    results.append(("qadam_frozen_step@vgg", "f32", gbs, us))
+    fmm = torch.zeros(nv, device="cuda")
+    gbs, us = bench(lambda: lib.fused_adam_step_segments(
+        fw, gq, offsets, fmm, fv, 200, 1e-3, 0.9, 0.999, 1e-8, 0.0, False),
+        28 * nv)
+    results.append(("  fused_adam_segments@vgg", "f32", gbs, us))
+    del fm, gq, wire, fw, fv, fmm
+
     # VGG16's first stage at the flagship's size, 32 x 224 x 224:
     # Conv2d(3, 64, 3, padding=1) + bias + ReLU as one kernel each way.
     # bytes: forward reads x and writes y; backward reads g, y and x

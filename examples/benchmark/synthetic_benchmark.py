@@ -44,6 +44,9 @@ def parse_args():
                    choices=GlobalAlgorithmRegistry.names())
     p.add_argument("--deterministic", action="store_true")
     p.add_argument("--fuse-optimizer", action="store_true")
+    p.add_argument("--fused-qadam", action="store_true",
+                   help="with --algorithm qadam: FusedQAdamOptimizer (HIP "
+                        "momentum-on-the-wire and frozen-variance step)")
     p.add_argument("--amp", action="store_true",
                    help="bf16 autocast (MI355X-native mixed precision)")
     p.add_argument("--async-sync-interval-ms", type=int, default=500)
@@ -72,10 +75,14 @@ def main():
         model = model.to(memory_format=torch.channels_last)
 
     if args.algorithm == "qadam":
-        from bagua_amd.parallel.algorithms.q_adam import QAdamOptimizer
+        from bagua_amd.parallel.algorithms.q_adam import (
+            FusedQAdamOptimizer,
+            QAdamOptimizer,
+        )
 
-        optimizer = QAdamOptimizer(model.parameters(), lr=0.01 * 0.1,
-                                   warmup_steps=100)
+        cls = FusedQAdamOptimizer if args.fused_qadam else QAdamOptimizer
+        optimizer = cls(model.parameters(), lr=0.01 * 0.1,
+                        warmup_steps=100)
         algorithm = GlobalAlgorithmRegistry.get("qadam")(optimizer)
     else:
         optimizer = torch.optim.SGD(model.parameters(), lr=0.01)
