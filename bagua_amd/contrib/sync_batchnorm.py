@@ -5,6 +5,11 @@ Horovod-derived).
 Forward reduces per-channel (sum, sqsum, count) with one allreduce;
 backward reduces (sum_dy, sum_dy_xmu). Works on CPU/gloo and GPU/RCCL
 through the same communication layer.
+
+On the GPU both directions run as the HIP kernels of ``ops/batchnorm.py``
+around those two allreduces, in the input's memory format (channels-last
+stays channels-last), whenever ``ops.batchnorm.kernels_apply`` takes the
+call; everything else runs the torch formulae below.
 """
 
 import torch
@@ -12,6 +17,7 @@ import torch.nn.functional as F
 from torch.nn.modules.batchnorm import _BatchNorm
 
 from ..communication import ReduceOp, allreduce_inplace
+from ..ops import batchnorm as bn_ops
 
 __all__ = ["SyncBatchNorm"]
 
@@ -64,6 +70,17 @@ class _SyncBatchNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, weight, bias, running_mean, running_var, eps,
                 momentum):
+        ctx.kernels = bn_ops.kernels_apply(input, weight, bias, running_mean,
+                                           running_var, momentum)
+        if ctx.kernels:
+            stats = bn_ops.stats(input)
+            allreduce_inplace(stats, op=ReduceOp.SUM)
+            out, mean_invstd = bn_ops.apply(
+                input, stats, weight, bias, running_mean, running_var,
+                momentum, eps)
+            ctx.save_for_backward(input, weight, bias, mean_invstd, stats)
+            return out
+
         input = input.contiguous()
         C = input.shape[1]
         reduce_dims = [0] + list(range(2, input.dim()))
@@ -102,6 +119,8 @@ class _SyncBatchNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output):
+        if ctx.kernels:
+            return _kernel_backward(ctx, grad_output)
         input, weight, mean, invstd, count = ctx.saved_tensors
         grad_output = grad_output.contiguous().float()
         C = input.shape[1]
@@ -131,3 +150,19 @@ class _SyncBatchNormFn(torch.autograd.Function):
         grad_input = ((term1 - term2 - term3) * invstd.view(shape)
                       * w).to(input.dtype)
         return grad_input, grad_weight, grad_bias, None, None, None, None
+
+
+def _kernel_backward(ctx, grad_output):
+    input, weight, bias, mean_invstd, stats = ctx.saved_tensors
+    with torch.no_grad():
+        grad_output = bn_ops.like_input(grad_output, input)
+        packed, grad_weight, grad_bias = bn_ops.backward_reduce(
+            grad_output, input, mean_invstd,
+            weight if ctx.needs_input_grad[1] else None,
+            bias if ctx.needs_input_grad[2] else None)
+        allreduce_inplace(packed, op=ReduceOp.SUM)
+        grad_input = None
+        if ctx.needs_input_grad[0]:
+            grad_input = bn_ops.backward_apply(
+                grad_output, input, packed, stats, mean_invstd, weight)
+    return grad_input, grad_weight, grad_bias, None, None, None, None

@@ -136,6 +136,31 @@ void bagua_epi_pool_relu_bwd_launch(int dtype, const void* g, const void* y,
                                     hipStream_t stream);
 }
 
+// batchnorm_kernels.hip launchers
+extern "C" {
+size_t bagua_bn_partial_rows(int dtype, int layout, size_t N, int C,
+                             size_t S);
+void bagua_bn_stats_launch(int dtype, int layout, const void* x,
+                           float* partial, float* stats, size_t N, int C,
+                           size_t S, hipStream_t stream);
+void bagua_bn_apply_launch(int dtype, int layout, const void* x, void* y,
+                           const float* stats, float* mean_invstd,
+                           const void* w, int w_f32, const void* b, int b_f32,
+                           void* rmean, void* rvar, int r_f32, float momentum,
+                           float one_minus_momentum, float eps, size_t N,
+                           int C, size_t S, hipStream_t stream);
+void bagua_bn_bwd_reduce_launch(int dtype, int layout, const void* dy,
+                                const void* x, const float* mean_invstd,
+                                float* partial, float* packed, void* gw,
+                                int gw_f32, void* gb, int gb_f32, size_t N,
+                                int C, size_t S, hipStream_t stream);
+void bagua_bn_bwd_apply_launch(int dtype, int layout, const void* dy,
+                               const void* x, void* dx, const float* packed,
+                               const float* stats, const float* mean_invstd,
+                               const void* w, int w_f32, size_t N, int C,
+                               size_t S, hipStream_t stream);
+}
+
 // first_conv_kernels.hip launchers
 extern "C" {
 size_t bagua_first_conv_partial_rows(int N, int H, int W);
@@ -1612,6 +1637,183 @@ static std::tuple<at::Tensor, at::Tensor> first_conv_bias_relu_bwd(
   return std::make_tuple(dw, db);
 }
 
+// ---------------------------------------------------------------------------
+// batch normalisation (batchnorm_kernels.hip): (N, C, ...) activations, seen
+// by the kernels as [rows, C] (channels-last 4-d, or inner size 1) or as
+// NCHW-contiguous [N, C, S]
+// ---------------------------------------------------------------------------
+
+// how the kernels see an activation; N counts rows and S is 1 with layout 0
+struct BnView {
+  int layout;  // 0 rows, 1 planes by element, 2 planes by 16 bytes
+  int64_t N, C, S;
+};
+
+static bool bn_aligned(const at::Tensor& t) {
+  return ((uintptr_t)t.data_ptr() & 15u) == 0;
+}
+
+static bool bn_channels_last(const at::Tensor& t) {
+  return t.dim() == 4 && !t.is_contiguous() &&
+         t.is_contiguous(at::MemoryFormat::ChannelsLast);
+}
+
+static BnView check_bn_act(const at::Tensor& x, const char* what) {
+  TORCH_CHECK(x.is_cuda(), what, " must be a GPU tensor");
+  kernel_dtype(x);
+  TORCH_CHECK(x.dim() >= 2 && x.numel() > 0 && x.numel() < kInt31, what,
+              " must be at least 2-d, not empty and below 2^31 elements");
+  const int64_t es = (int64_t)x.element_size();
+  BnView v;
+  v.N = x.size(0);
+  v.C = x.size(1);
+  v.S = x.numel() / (v.N * v.C);
+  if (bn_channels_last(x) || (v.S == 1 && x.is_contiguous())) {
+    TORCH_CHECK(v.C % (16 / es) == 0 && bn_aligned(x), what,
+                ": rows of channels need C a multiple of ", 16 / es,
+                " and a 16-byte aligned base");
+    v.layout = 0;
+    v.N *= v.S;
+    v.S = 1;
+  } else {
+    TORCH_CHECK(x.is_contiguous(), what,
+                " must be contiguous or 4-d channels-last");
+    v.layout = ((v.S * es) % 16 == 0 && bn_aligned(x)) ? 2 : 1;
+  }
+  return v;
+}
+
+// t goes through the same kernel as x; a misaligned t takes 16-byte loads
+// away from the planes layout
+static void check_bn_like(const at::Tensor& t, const at::Tensor& x,
+                          BnView& v, const char* what) {
+  TORCH_CHECK(t.sizes() == x.sizes() &&
+                  t.scalar_type() == x.scalar_type() &&
+                  t.device() == x.device(),
+              what, ": shape, dtype or device mismatch");
+  TORCH_CHECK(bn_channels_last(x)
+                  ? t.is_contiguous(at::MemoryFormat::ChannelsLast)
+                  : t.is_contiguous(),
+              what, " must have the activation's memory format");
+  if (v.layout == 0) {
+    TORCH_CHECK(bn_aligned(t), what, " must be 16-byte aligned");
+  } else if (!bn_aligned(t)) {
+    v.layout = 1;
+  }
+}
+
+// f32 vector of `numel` elements next to the activation x
+static float* check_bn_f32(const at::Tensor& t, int64_t numel,
+                           const at::Tensor& x, const char* what) {
+  check_device_contig(t);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 1 &&
+                  t.size(0) == numel && t.device() == x.device(),
+              what, " must be ", numel, " f32 elements on the activation's "
+              "device");
+  return (float*)t.data_ptr();
+}
+
+// optional per-channel vector, f32 or in the activation's dtype
+static void* check_bn_channels(const std::optional<at::Tensor>& t,
+                               const at::Tensor& x, int* is_f32,
+                               const char* what) {
+  *is_f32 = 0;
+  if (!t.has_value()) return nullptr;
+  check_device_contig(*t);
+  TORCH_CHECK(t->dim() == 1 && t->size(0) == x.size(1) &&
+                  t->device() == x.device() &&
+                  (t->scalar_type() == at::kFloat ||
+                   t->scalar_type() == x.scalar_type()),
+              what, " must be 1-d of C elements, f32 or in the activation's "
+              "dtype, on its device");
+  *is_f32 = t->scalar_type() == at::kFloat;
+  return t->data_ptr();
+}
+
+// f32 [blocks, 2C] scratch of the two-stage sums; from torch's allocator,
+// so a captured graph keeps it
+static at::Tensor bn_partial(const at::Tensor& x, const BnView& v) {
+  const int64_t blocks = (int64_t)bagua_bn_partial_rows(
+      kernel_dtype(x), v.layout, (size_t)v.N, (int)v.C, (size_t)v.S);
+  return at::empty({blocks, 2 * v.C}, x.options().dtype(at::kFloat));
+}
+
+// stats = (sum x [C], sum x^2 [C], local element count per channel)
+static void bn_stats(at::Tensor x, at::Tensor stats) {
+  const BnView v = check_bn_act(x, "x");
+  float* st = check_bn_f32(stats, 2 * v.C + 1, x, "stats");
+  at::Tensor partial = bn_partial(x, v);
+  bagua_bn_stats_launch(kernel_dtype(x), v.layout, x.data_ptr(),
+                        (float*)partial.data_ptr(), st, (size_t)v.N,
+                        (int)v.C, (size_t)v.S, current_stream());
+}
+
+// y = (x - mean) * invstd * weight + bias from the (allreduced) stats;
+// fills mean_invstd [2C] and moves the running statistics in place
+static void bn_apply(at::Tensor x, at::Tensor y, at::Tensor stats,
+                     at::Tensor mean_invstd,
+                     std::optional<at::Tensor> weight,
+                     std::optional<at::Tensor> bias,
+                     std::optional<at::Tensor> running_mean,
+                     std::optional<at::Tensor> running_var, double momentum,
+                     double eps) {
+  BnView v = check_bn_act(x, "x");
+  check_bn_like(y, x, v, "y");
+  const float* st = check_bn_f32(stats, 2 * v.C + 1, x, "stats");
+  float* mi = check_bn_f32(mean_invstd, 2 * v.C, x, "mean_invstd");
+  int w_f32, b_f32, r_f32, rv_f32;
+  const void* w = check_bn_channels(weight, x, &w_f32, "weight");
+  const void* b = check_bn_channels(bias, x, &b_f32, "bias");
+  void* rm = check_bn_channels(running_mean, x, &r_f32, "running_mean");
+  void* rv = check_bn_channels(running_var, x, &rv_f32, "running_var");
+  TORCH_CHECK((rm == nullptr) == (rv == nullptr) && r_f32 == rv_f32,
+              "running_mean and running_var go together, in one dtype");
+  bagua_bn_apply_launch(kernel_dtype(x), v.layout, x.data_ptr(),
+                        y.data_ptr(), st, mi, w, w_f32, b, b_f32, rm, rv,
+                        r_f32, (float)momentum, (float)(1.0 - momentum),
+                        (float)eps, (size_t)v.N, (int)v.C, (size_t)v.S,
+                        current_stream());
+}
+
+// packed = (sum dy [C], sum dy * (x - mean) [C]); from these local sums
+// grad_bias = sum dy and grad_weight = sum dy * (x - mean) * invstd
+static void bn_backward_reduce(at::Tensor dy, at::Tensor x,
+                               at::Tensor mean_invstd, at::Tensor packed,
+                               std::optional<at::Tensor> grad_weight,
+                               std::optional<at::Tensor> grad_bias) {
+  BnView v = check_bn_act(x, "x");
+  check_bn_like(dy, x, v, "dy");
+  const float* mi = check_bn_f32(mean_invstd, 2 * v.C, x, "mean_invstd");
+  float* pk = check_bn_f32(packed, 2 * v.C, x, "packed");
+  int gw_f32, gb_f32;
+  void* gw = check_bn_channels(grad_weight, x, &gw_f32, "grad_weight");
+  void* gb = check_bn_channels(grad_bias, x, &gb_f32, "grad_bias");
+  at::Tensor partial = bn_partial(x, v);
+  bagua_bn_bwd_reduce_launch(kernel_dtype(x), v.layout, dy.data_ptr(),
+                             x.data_ptr(), mi, (float*)partial.data_ptr(),
+                             pk, gw, gw_f32, gb, gb_f32, (size_t)v.N,
+                             (int)v.C, (size_t)v.S, current_stream());
+}
+
+// dx from the (allreduced) packed sums and the count in stats[2C]
+static void bn_backward_apply(at::Tensor dy, at::Tensor x, at::Tensor dx,
+                              at::Tensor packed, at::Tensor stats,
+                              at::Tensor mean_invstd,
+                              std::optional<at::Tensor> weight) {
+  BnView v = check_bn_act(x, "x");
+  check_bn_like(dy, x, v, "dy");
+  check_bn_like(dx, x, v, "dx");
+  const float* pk = check_bn_f32(packed, 2 * v.C, x, "packed");
+  const float* st = check_bn_f32(stats, 2 * v.C + 1, x, "stats");
+  const float* mi = check_bn_f32(mean_invstd, 2 * v.C, x, "mean_invstd");
+  int w_f32;
+  const void* w = check_bn_channels(weight, x, &w_f32, "weight");
+  bagua_bn_bwd_apply_launch(kernel_dtype(x), v.layout, dy.data_ptr(),
+                            x.data_ptr(), dx.data_ptr(), pk, st, mi, w,
+                            w_f32, (size_t)v.N, (int)v.C, (size_t)v.S,
+                            current_stream());
+}
+
 static py::bytes nccl_unique_id() {
   ncclUniqueId id;
   NCCL_CHECK(ncclGetUniqueId(&id));
@@ -1931,4 +2133,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("weight"), py::arg("bias"));
   m.def("first_conv_bias_relu_bwd", &first_conv_bias_relu_bwd, py::arg("g"),
         py::arg("y"), py::arg("x"), py::arg("weight_like"));
+  m.def("bn_stats", &bn_stats, py::arg("x"), py::arg("stats"));
+  m.def("bn_apply", &bn_apply, py::arg("x"), py::arg("y"), py::arg("stats"),
+        py::arg("mean_invstd"), py::arg("weight") = py::none(),
+        py::arg("bias") = py::none(), py::arg("running_mean") = py::none(),
+        py::arg("running_var") = py::none(), py::arg("momentum") = 0.1,
+        py::arg("eps") = 1e-5);
+  m.def("bn_backward_reduce", &bn_backward_reduce, py::arg("dy"),
+        py::arg("x"), py::arg("mean_invstd"), py::arg("packed"),
+        py::arg("grad_weight") = py::none(),
+        py::arg("grad_bias") = py::none());
+  m.def("bn_backward_apply", &bn_backward_apply, py::arg("dy"), py::arg("x"),
+        py::arg("dx"), py::arg("packed"), py::arg("stats"),
+        py::arg("mean_invstd"), py::arg("weight") = py::none());
 }

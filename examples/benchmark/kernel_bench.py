@@ -29,6 +29,81 @@ def bench(fn, bytes_moved, iters=50, warmup=10):
     return bytes_moved / dt / 1e9, dt * 1e6
 
 
+def sync_batchnorm_rows():
+    """SyncBatchNorm's kernels at ResNet-50's BN shapes (bf16 channels-last,
+    batch 32) and VGG-bn's first (f32 NCHW, batch 8), each next to the torch
+    chain it replaces on the same tensors. Bytes are the passes the
+    algorithm needs in the input's dtype: stats reads x, apply reads x and
+    writes y (3 passes forward), bwd_reduce reads dy and x, bwd_apply reads
+    dy and x and writes dx (5 backward); the chain's rows count the same
+    bytes."""
+    from bagua_amd.contrib import sync_batchnorm
+    from bagua_amd.ops import batchnorm as bn_ops
+
+    rows = []
+    shapes = [(torch.bfloat16, True, (32, 64, 112, 112)),
+              (torch.bfloat16, True, (32, 256, 56, 56)),
+              (torch.bfloat16, True, (32, 512, 28, 28)),
+              (torch.bfloat16, True, (32, 2048, 7, 7)),
+              (torch.float32, False, (8, 64, 224, 224))]
+    for dtype, cl, shape in shapes:
+        c = shape[1]
+        name = "bf16" if dtype == torch.bfloat16 else "f32"
+        tag = "@%dx%dx%d%s" % (c, shape[2], shape[3], "cl" if cl else "")
+        fmt = torch.channels_last if cl else torch.contiguous_format
+        x = torch.randn(shape, device="cuda").to(dtype).contiguous(
+            memory_format=fmt)
+        dy = torch.randn_like(x)
+        w = torch.rand(c, device="cuda") + 0.5
+        b = torch.randn(c, device="cuda")
+        rm, rv = torch.zeros(c, device="cuda"), torch.ones(c, device="cuda")
+        nbytes = x.numel() * x.element_size()
+        assert bn_ops.kernels_apply(x, w, b, rm, rv, 0.1)
+        stats = bn_ops.stats(x)
+        _, mi = bn_ops.apply(x, stats, w, b, rm, rv, 0.1, 1e-5)
+        packed, _, _ = bn_ops.backward_reduce(dy, x, mi, w, b)
+
+        # the module's function both ways, kernels and the torch chain
+        # they replace, alternating, twice for the spread; no allreduce in
+        # either (a world of one rank)
+        fn = sync_batchnorm._SyncBatchNormFn
+        leaves = [t.clone().requires_grad_() for t in (x, w, b)]
+
+        def forward():
+            with torch.no_grad():
+                return fn.apply(x, w, b, rm, rv, 1e-5, 0.1)
+
+        def both():
+            y = fn.apply(*leaves, rm, rv, 1e-5, 0.1)
+            return torch.autograd.grad(y, leaves, dy)
+
+        saved = (bn_ops.kernels_apply, sync_batchnorm.allreduce_inplace)
+        sync_batchnorm.allreduce_inplace = lambda t, op=None: None
+        try:
+            for _ in range(2):
+                for label, call, passes in (("fwd", forward, 3),
+                                            ("fwd+bwd", both, 8)):
+                    bn_ops.kernels_apply = saved[0]
+                    gbs, us = bench(call, passes * nbytes)
+                    rows.append(("bn_" + label + tag, name, gbs, us))
+                    bn_ops.kernels_apply = lambda *a, **k: False
+                    gbs, us = bench(call, passes * nbytes)
+                    rows.append(("  torch chain " + label, name, gbs, us))
+        finally:
+            bn_ops.kernels_apply, sync_batchnorm.allreduce_inplace = saved
+        for label, call, passes in (
+                ("bn_stats", lambda: bn_ops.stats(x), 1),
+                ("bn_apply", lambda: bn_ops.apply(
+                    x, stats, w, b, rm, rv, 0.1, 1e-5), 2),
+                ("bn_bwd_reduce", lambda: bn_ops.backward_reduce(
+                    dy, x, mi, w, b), 2),
+                ("bn_bwd_apply", lambda: bn_ops.backward_apply(
+                    dy, x, packed, stats, mi, w), 3)):
+            gbs, us = bench(call, passes * nbytes)
+            rows.append((label + tag, name, gbs, us))
+    return rows
+
+
 def main():
     lib = native.require()
     n = 1 << 26  # 64 Mi elements
@@ -178,6 +253,9 @@ def main():
     gbs, us = bench(lambda: lib.first_conv_bias_relu_bwd(go, yo, xi, wt),
                     (2 * yo.numel() + xi.numel()) * es)
     results.append(("first_conv_bwd@vgg", "bf16", gbs, us))
+
+    del xi, wt, bs, yo, go
+    results.extend(sync_batchnorm_rows())
 
     print("%-24s %-5s %10s %10s" % ("kernel", "dtype", "GB/s", "us"))
     for name, dt, gbs, us in results:
