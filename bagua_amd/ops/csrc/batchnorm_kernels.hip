@@ -42,10 +42,11 @@
 //          a multiple of 16 and the bases are aligned, else 1: any C and S.
 //          Block sums are wave64 shuffles, then LDS across the four waves.
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>  // by name in every .hip file: see device_util.h
 #include <cmath>
-#include <cstdint>
+
+#include "device_util.h"  // to_f / from_f (bf16 is bf16_t), NO_PACKED_F32
+#include "launchers.h"
 
 #define BN_BLOCK 256
 // row-blocks of the rows-layout apply kernels
@@ -62,46 +63,10 @@
 
 // Like the newer kernels of kernels.hip, these are built without packed
 // f32 arithmetic; they are bound by memory and lose nothing by it.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define BN_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define BN_NO_PACKED_F32  // the host pass does not know the feature
-#endif
 #define BN_KERNEL \
-  __global__ void __launch_bounds__(BN_BLOCK) BN_NO_PACKED_F32
+  __global__ void __launch_bounds__(BN_BLOCK) NO_PACKED_F32
 
 namespace {
-
-struct bf16_t {
-  uint16_t bits;
-};
-
-template <typename T> __device__ __forceinline__ float to_f(T v);
-template <> __device__ __forceinline__ float to_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f<__half>(__half v) {
-  return __half2float(v);
-}
-template <> __device__ __forceinline__ float to_f<bf16_t>(bf16_t v) {
-  return __uint_as_float((uint32_t)v.bits << 16);
-}
-
-template <typename T> __device__ __forceinline__ T from_f(float v);
-template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ __half from_f<__half>(float v) {
-  return __float2half(v);
-}
-// torch's rounding (c10 round_to_nearest_even), NaN payload included; the
-// same as in epilogue_kernels.hip
-template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float v) {
-  bf16_t r;
-  if (v != v) {
-    r.bits = 0x7FC0;
-  } else {
-    const uint32_t u = __float_as_uint(v);
-    r.bits = (uint16_t)((u + ((u >> 16) & 1u) + 0x7FFFu) >> 16);
-  }
-  return r;
-}
 
 // V elements loaded at once: 16 bytes, or one element
 template <typename T, int V> struct alignas(sizeof(T) * V) Pack {
@@ -790,30 +755,14 @@ void bwd_apply_t(int layout, const void* dy, const void* x, void* dx,
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// launchers (dtype: 0=f32 1=f16 2=bf16; layout as above). The caller has
-// checked: N * C * S is positive and below 2^31; with layout 0, C is a
-// multiple of the 16-byte vector, S is 1 (N counts rows) and the data
-// pointers are 16-byte aligned; with layout 2, S * sizeof(T) is a multiple
-// of 16 and the data pointers are aligned. *_f32 say whether a per-channel
-// vector is f32 (else it has the data's dtype).
+// launchers; what the caller has checked is in launchers.h
 // ---------------------------------------------------------------------------
-
-#define BN_DISPATCH(dtype, fn, ...)                                        \
-  do {                                                                     \
-    if ((dtype) == 0)                                                      \
-      fn<float>(__VA_ARGS__);                                              \
-    else if ((dtype) == 1)                                                 \
-      fn<__half>(__VA_ARGS__);                                             \
-    else                                                                   \
-      fn<bf16_t>(__VA_ARGS__);                                             \
-  } while (0)
 
 extern "C" {
 
-// rows of the f32 partial buffer [rows, 2C] that the reducing launchers need
 size_t bagua_bn_partial_rows(int dtype, int layout, size_t N, int C,
                              size_t S) {
-  const int V = dtype == 0 ? 4 : 8;
+  const int V = dtype == BAGUA_F32 ? 4 : 8;
   if (layout == 0) {
     const int CVtot = C / V;
     const int tiles = (CVtot + BN_BLOCK - 1) / BN_BLOCK;
@@ -823,14 +772,13 @@ size_t bagua_bn_partial_rows(int dtype, int layout, size_t N, int C,
   return plane_splits(N * (layout == 2 ? S / V : S), C);
 }
 
-// stats = (sum x [C], sum x*x [C], N*S)
 void bagua_bn_stats_launch(int dtype, int layout, const void* x,
                            float* partial, float* stats, size_t N, int C,
                            size_t S, hipStream_t stream) {
-  BN_DISPATCH(dtype, stats_t, layout, x, partial, stats, N, C, S, stream);
+  DISPATCH_DTYPE(dtype, bf16_t, stats_t, layout, x, partial, stats, N, C, S,
+                 stream);
 }
 
-// w, b and rmean/rvar may be null
 void bagua_bn_apply_launch(int dtype, int layout, const void* x, void* y,
                            const float* stats, float* mean_invstd,
                            const void* w, int w_f32, const void* b, int b_f32,
@@ -848,28 +796,26 @@ void bagua_bn_apply_launch(int dtype, int layout, const void* x, void* y,
   p.momentum = momentum;
   p.one_minus_momentum = one_minus_momentum;
   p.eps = eps;
-  BN_DISPATCH(dtype, apply_t, layout, x, y, stats, mean_invstd, N, C, S, p,
-              stream);
+  DISPATCH_DTYPE(dtype, bf16_t, apply_t, layout, x, y, stats, mean_invstd, N,
+                 C, S, p, stream);
 }
 
-// packed = (sum dy [C], sum dy*(x-mean) [C]); gw and gb may be null
 void bagua_bn_bwd_reduce_launch(int dtype, int layout, const void* dy,
                                 const void* x, const float* mean_invstd,
                                 float* partial, float* packed, void* gw,
                                 int gw_f32, void* gb, int gb_f32, size_t N,
                                 int C, size_t S, hipStream_t stream) {
-  BN_DISPATCH(dtype, bwd_reduce_t, layout, dy, x, mean_invstd, partial,
-              packed, gw, gw_f32, gb, gb_f32, N, C, S, stream);
+  DISPATCH_DTYPE(dtype, bf16_t, bwd_reduce_t, layout, dy, x, mean_invstd,
+                 partial, packed, gw, gw_f32, gb, gb_f32, N, C, S, stream);
 }
 
-// w may be null
 void bagua_bn_bwd_apply_launch(int dtype, int layout, const void* dy,
                                const void* x, void* dx, const float* packed,
                                const float* stats, const float* mean_invstd,
                                const void* w, int w_f32, size_t N, int C,
                                size_t S, hipStream_t stream) {
-  BN_DISPATCH(dtype, bwd_apply_t, layout, dy, x, dx, packed, stats,
-              mean_invstd, w, w_f32, N, C, S, stream);
+  DISPATCH_DTYPE(dtype, bf16_t, bwd_apply_t, layout, dy, x, dx, packed, stats,
+                 mean_invstd, w, w_f32, N, C, S, stream);
 }
 
 }  // extern "C"

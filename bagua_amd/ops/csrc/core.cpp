@@ -29,151 +29,7 @@
 #include <tuple>
 #include <vector>
 
-// kernels.hip launchers
-extern "C" {
-void bagua_ew_launch(int op, int dtype, void* x, const void* y, float f,
-                     size_t n, hipStream_t stream);
-void bagua_async_avg_launch(int dtype, void* x, const void* reduced,
-                            const void* x_copy, float nranks, size_t n,
-                            hipStream_t stream);
-void bagua_reduce_chunk_launch(int dtype, void* x, int num_chunks,
-                               int target_chunk, int average, size_t chunk,
-                               hipStream_t stream);
-void bagua_compress_launch(int dtype, const void* x, uint8_t* out,
-                           uint32_t* scratch, uint32_t* partials,
-                           size_t chunk, size_t chunk_stride,
-                           int num_chunks_total, int chunk_begin,
-                           int chunk_count, hipStream_t stream);
-void bagua_decompress_launch(int dtype, const uint8_t* in, void* x,
-                             size_t chunk, size_t chunk_stride,
-                             int chunk_begin, int chunk_count,
-                             hipStream_t stream);
-void bagua_dequant_reduce_launch(int dtype, const uint8_t* in, void* x,
-                                 size_t chunk, size_t chunk_stride,
-                                 int num_chunks, int target_chunk,
-                                 int average, hipStream_t stream);
-void bagua_fused_sgd_launch(float* p, const float* g, float* m, float lr,
-                            float momentum, float dampening,
-                            float weight_decay, int nesterov,
-                            int momentum_initialized, size_t n,
-                            hipStream_t stream);
-void bagua_fused_adam_launch(float* p, const float* g, float* m, float* v,
-                             float lr, float beta1, float beta2,
-                             float one_minus_beta1, float one_minus_beta2,
-                             float eps, float weight_decay, int adamw,
-                             float bc1, float bc2, size_t n,
-                             hipStream_t stream);
-void bagua_fused_sgd_mixed_launch(void* p, const void* g, float* master,
-                                  float* m, float lr, float momentum,
-                                  float dampening, float weight_decay,
-                                  int nesterov, int momentum_initialized,
-                                  size_t n, hipStream_t stream);
-void bagua_fused_sgd_segments_launch(float* p, float* m, float lr,
-                                     float momentum, float dampening,
-                                     float weight_decay, int nesterov,
-                                     int momentum_initialized,
-                                     const void* const* grads,
-                                     const size_t* begins,
-                                     const size_t* numels, size_t count,
-                                     hipStream_t stream);
-void bagua_fused_sgd_mixed_segments_launch(
-    void* p, float* master, float* m, float lr, float momentum,
-    float dampening, float weight_decay, int nesterov,
-    int momentum_initialized, const void* const* grads, const size_t* begins,
-    const size_t* numels, size_t count, hipStream_t stream);
-void bagua_fused_adam_segments_launch(
-    float* p, float* m, float* v, float lr, float beta1, float beta2,
-    float one_minus_beta1, float one_minus_beta2, float eps,
-    float weight_decay, int adamw, float bc1, float bc2,
-    const void* const* grads, const size_t* begins, const size_t* numels,
-    size_t count, hipStream_t stream);
-size_t bagua_qadam_momentum_max_segments();
-void bagua_qadam_momentum_compress_launch(
-    float* m, const void* const* grads, const size_t* begins,
-    const size_t* numels, size_t count, float beta1, float one_minus_beta1,
-    uint8_t* out, uint32_t* scratch, uint32_t* partials, size_t chunk,
-    size_t chunk_stride, int num_chunks, hipStream_t stream);
-void bagua_qadam_frozen_segments_launch(
-    float* p, const float* v, float lr, float eps, float bc1, float bc2,
-    const void* const* moms, const size_t* begins, const size_t* numels,
-    size_t count, hipStream_t stream);
-}
-
-// moe_kernels.hip launchers
-extern "C" {
-size_t bagua_moe_assign_workspace(int S, int E);
-void bagua_moe_assign_slots_launch(const int* expert, int S, int E,
-                                   int capacity, const int* base, int* hist,
-                                   int* slot, int* counts, int* src,
-                                   hipStream_t stream);
-void bagua_moe_gather_rows_launch(int dtype, const void* x, const int* src,
-                                  void* out, const float* w, const int* dest,
-                                  int k, int S, size_t R, int M,
-                                  hipStream_t stream);
-void bagua_moe_combine_rows_launch(int dtype, const void* eo,
-                                   const int* dest, void* out,
-                                   const float* w, int k, int S, size_t R,
-                                   int M, hipStream_t stream);
-void bagua_moe_row_dot_launch(int dtype, const void* g, const void* eo,
-                              const int* dest, float* gw, int k, int S,
-                              size_t R, int M, hipStream_t stream);
-}
-
-// epilogue_kernels.hip launchers
-extern "C" {
-size_t bagua_epi_partial_rows(int dtype, size_t work_rows, int C);
-void bagua_epi_bias_relu_launch(int dtype, void* x, const void* bias,
-                                size_t rows, int C, hipStream_t stream);
-void bagua_epi_bias_relu_pool_launch(int dtype, void* x, const void* bias,
-                                     void* p, size_t orows, int Wo, int C,
-                                     hipStream_t stream);
-void bagua_epi_relu_bwd_launch(int dtype, const void* g, const void* y,
-                               void* dx, float* partial, void* db,
-                               size_t rows, int C, hipStream_t stream);
-void bagua_epi_pool_relu_bwd_launch(int dtype, const void* g, const void* y,
-                                    void* dx, float* partial, void* db,
-                                    size_t orows, int Wo, int C,
-                                    hipStream_t stream);
-}
-
-// batchnorm_kernels.hip launchers
-extern "C" {
-size_t bagua_bn_partial_rows(int dtype, int layout, size_t N, int C,
-                             size_t S);
-void bagua_bn_stats_launch(int dtype, int layout, const void* x,
-                           float* partial, float* stats, size_t N, int C,
-                           size_t S, hipStream_t stream);
-void bagua_bn_apply_launch(int dtype, int layout, const void* x, void* y,
-                           const float* stats, float* mean_invstd,
-                           const void* w, int w_f32, const void* b, int b_f32,
-                           void* rmean, void* rvar, int r_f32, float momentum,
-                           float one_minus_momentum, float eps, size_t N,
-                           int C, size_t S, hipStream_t stream);
-void bagua_bn_bwd_reduce_launch(int dtype, int layout, const void* dy,
-                                const void* x, const float* mean_invstd,
-                                float* partial, float* packed, void* gw,
-                                int gw_f32, void* gb, int gb_f32, size_t N,
-                                int C, size_t S, hipStream_t stream);
-void bagua_bn_bwd_apply_launch(int dtype, int layout, const void* dy,
-                               const void* x, void* dx, const float* packed,
-                               const float* stats, const float* mean_invstd,
-                               const void* w, int w_f32, size_t N, int C,
-                               size_t S, hipStream_t stream);
-}
-
-// first_conv_kernels.hip launchers
-extern "C" {
-size_t bagua_first_conv_partial_rows(int N, int H, int W);
-size_t bagua_first_conv_partial_cols();
-void bagua_first_conv_fwd_launch(const void* x, const void* w,
-                                 const long* wstride, const void* bias,
-                                 void* y, int N, int H, int W,
-                                 hipStream_t stream);
-void bagua_first_conv_bwd_launch(const void* g, const void* y, const void* x,
-                                 float* partial, void* dw,
-                                 const long* wstride, void* db, int N, int H,
-                                 int W, hipStream_t stream);
-}
+#include "launchers.h"  // every launcher of the .hip files, the dtype codes
 
 #define HIP_CHECK(cmd)                                                    \
   do {                                                                    \
@@ -220,12 +76,12 @@ ncclRedOp_t nccl_op(int op) {
   }
 }
 
-// kernel dtype code: 0=f32 1=f16 2=bf16
+// the launchers' dtype code (launchers.h)
 int kernel_dtype(const at::Tensor& t) {
   switch (t.scalar_type()) {
-    case at::kFloat: return 0;
-    case at::kHalf: return 1;
-    case at::kBFloat16: return 2;
+    case at::kFloat: return BAGUA_F32;
+    case at::kHalf: return BAGUA_F16;
+    case at::kBFloat16: return BAGUA_BF16;
     default:
       throw std::runtime_error("kernel supports f32/f16/bf16 only");
   }
@@ -813,12 +669,6 @@ class BucketExecutor {
 // Opt-in (BAGUA_P2P_ALLTOALL=1 wires it into the scattergather/ByteGrad
 // chunk exchange); default stays on ncclAllToAll.
 // ---------------------------------------------------------------------------
-
-extern "C" void bagua_p2p_barrier_launch(void* peer_flags_dev_array,
-                                         void* my_flags, int rank,
-                                         int nranks,
-                                         unsigned long long seq,
-                                         hipStream_t stream);
 
 class P2PAlltoAll {
  public:

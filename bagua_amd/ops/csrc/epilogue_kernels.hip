@@ -31,10 +31,11 @@
 // [blocks, C] f32 buffer, and a second kernel that sums the rows in a fixed
 // order and rounds once to T.
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>  // by name in every .hip file: see device_util.h
 #include <cmath>
-#include <cstdint>
+
+#include "device_util.h"  // to_f / from_f (bf16 is bf16_t), Vec16
+#include "launchers.h"
 
 #define EPI_BLOCK 256
 #define EPI_MAX_GRID 2048
@@ -43,41 +44,6 @@
 #define EPI_FIN_SL (EPI_BLOCK / EPI_FIN_CH)
 
 namespace {
-
-struct bf16_t {
-  uint16_t bits;
-};
-
-template <typename T> __device__ __forceinline__ float to_f(T v);
-template <> __device__ __forceinline__ float to_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f<__half>(__half v) {
-  return __half2float(v);
-}
-template <> __device__ __forceinline__ float to_f<bf16_t>(bf16_t v) {
-  return __uint_as_float((uint32_t)v.bits << 16);
-}
-
-template <typename T> __device__ __forceinline__ T from_f(float v);
-template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ __half from_f<__half>(float v) {
-  return __float2half(v);
-}
-// torch's rounding (c10 round_to_nearest_even), NaN payload included
-template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float v) {
-  bf16_t r;
-  if (v != v) {
-    r.bits = 0x7FC0;
-  } else {
-    const uint32_t u = __float_as_uint(v);
-    r.bits = (uint16_t)((u + ((u >> 16) & 1u) + 0x7FFFu) >> 16);
-  }
-  return r;
-}
-
-template <typename T> struct alignas(16) Vec16 {
-  static constexpr int N = 16 / sizeof(T);
-  T v[N];
-};
 
 // relu(T(x + b)) as add_ then clamp_min_(0) give it
 template <typename T>
@@ -445,57 +411,43 @@ void pool_relu_bwd_t(const void* g, const void* y, void* dx, float* partial,
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// launchers (dtype: 0=f32 1=f16 2=bf16). The caller has checked: C is a
-// multiple of the 16-byte vector and C / vector <= 256, full-size rows are
-// below 2^31, data pointers are 16-byte aligned, H and W are even when
-// pooling. `rows` counts full-size rows, `orows` pooled ones.
+// launchers; what the caller has checked is in launchers.h
 // ---------------------------------------------------------------------------
-
-#define EPI_DISPATCH(dtype, fn, ...)                                       \
-  do {                                                                     \
-    if ((dtype) == 0)                                                      \
-      fn<float>(__VA_ARGS__);                                              \
-    else if ((dtype) == 1)                                                 \
-      fn<__half>(__VA_ARGS__);                                             \
-    else                                                                   \
-      fn<bf16_t>(__VA_ARGS__);                                             \
-  } while (0)
 
 extern "C" {
 
-// rows of the f32 partial buffer [blocks, C] the backward launchers need;
-// work_rows is `rows` without pooling and `orows` with it
 size_t bagua_epi_partial_rows(int dtype, size_t work_rows, int C) {
-  const int V = dtype == 0 ? 4 : 8;
+  const int V = dtype == BAGUA_F32 ? 4 : 8;
   return grid_for(work_rows, EPI_BLOCK / (C / V), reduce_cap(C));
 }
 
 void bagua_epi_bias_relu_launch(int dtype, void* x, const void* bias,
                                 size_t rows, int C, hipStream_t stream) {
   if (rows == 0) return;
-  EPI_DISPATCH(dtype, bias_relu_t, x, bias, rows, C, stream);
+  DISPATCH_DTYPE(dtype, bf16_t, bias_relu_t, x, bias, rows, C, stream);
 }
 
 void bagua_epi_bias_relu_pool_launch(int dtype, void* x, const void* bias,
                                      void* p, size_t orows, int Wo, int C,
                                      hipStream_t stream) {
   if (orows == 0) return;
-  EPI_DISPATCH(dtype, bias_relu_pool_t, x, bias, p, orows, Wo, C, stream);
+  DISPATCH_DTYPE(dtype, bf16_t, bias_relu_pool_t, x, bias, p, orows, Wo, C,
+                 stream);
 }
 
-// partial == nullptr: dx only, db is left alone
 void bagua_epi_relu_bwd_launch(int dtype, const void* g, const void* y,
                                void* dx, float* partial, void* db,
                                size_t rows, int C, hipStream_t stream) {
-  EPI_DISPATCH(dtype, relu_bwd_t, g, y, dx, partial, db, rows, C, stream);
+  DISPATCH_DTYPE(dtype, bf16_t, relu_bwd_t, g, y, dx, partial, db, rows, C,
+                 stream);
 }
 
 void bagua_epi_pool_relu_bwd_launch(int dtype, const void* g, const void* y,
                                     void* dx, float* partial, void* db,
                                     size_t orows, int Wo, int C,
                                     hipStream_t stream) {
-  EPI_DISPATCH(dtype, pool_relu_bwd_t, g, y, dx, partial, db, orows, Wo, C,
-               stream);
+  DISPATCH_DTYPE(dtype, bf16_t, pool_relu_bwd_t, g, y, dx, partial, db, orows,
+                 Wo, C, stream);
 }
 
 }  // extern "C"

@@ -36,8 +36,10 @@
 //              bf16 and writes dW through the weight's strides. No atomics:
 //              two runs give the same bits.
 
-#include <hip/hip_runtime.h>
-#include <cstdint>
+#include <hip/hip_runtime.h>  // by name in every .hip file: see device_util.h
+
+#include "device_util.h"  // bf16_to_f / f_to_bf16 on raw uint16_t
+#include "launchers.h"
 
 #define FC_BLOCK 256
 #define FC_WAVES (FC_BLOCK / 64)
@@ -69,17 +71,6 @@ union Frag {
   uint16_t e[8];
   uint4 q;
 };
-
-__device__ __forceinline__ float bf16_to_f(uint16_t b) {
-  return __uint_as_float((uint32_t)b << 16);
-}
-
-// torch's rounding (c10 round_to_nearest_even), NaN payload included
-__device__ __forceinline__ uint16_t f_to_bf16(float v) {
-  if (v != v) return 0x7FC0;
-  const uint32_t u = __float_as_uint(v);
-  return (uint16_t)((u + ((u >> 16) & 1u) + 0x7FFFu) >> 16);
-}
 
 // relu(bf16(x + b)) as add_ then clamp_min_(0) give it
 __device__ __forceinline__ uint16_t bias_relu(uint16_t x, float b) {
@@ -457,15 +448,12 @@ inline unsigned grid_of(const Geom& g, int cap) {
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// launchers. The caller has checked: bf16, x (N, 3, H, W) and g, y
-// (N, 64, H, W) channels-last contiguous, g and y 16-byte aligned,
-// 1 <= N*H*W < 2^31, the weight's (co, ci, ky, kx) strides address 64*27
-// distinct elements.
+// launchers; what the caller has checked is in launchers.h
 // ---------------------------------------------------------------------------
 
 extern "C" {
 
-// rows of the f32 partial buffer [blocks, 64 * 28] the backward needs
+// the f32 partial buffer is [blocks, 64 * 28]
 size_t bagua_first_conv_partial_rows(int N, int H, int W) {
   return grid_of(geom_of(N, H, W), FC_BWD_MAX_GRID);
 }

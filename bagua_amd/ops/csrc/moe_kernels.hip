@@ -22,10 +22,10 @@
 //    per lane when rows are 16-byte aligned, f32 math for f16/bf16 rows,
 //    weights always f32; row offsets in size_t.
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_bf16.h>
-#include <cstdint>
+#include <hip/hip_runtime.h>  // by name in every .hip file: see device_util.h
+
+#include "device_util.h"  // to_f / from_f (bf16 is __hip_bfloat16), Vec16
+#include "launchers.h"
 
 #define MOE_BLOCK 256
 #define MOE_WAVE 64
@@ -33,29 +33,6 @@
 #define MOE_MAX_GRID 16384
 
 namespace {
-
-template <typename T> __device__ __forceinline__ float to_f(T v);
-template <> __device__ __forceinline__ float to_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f<__half>(__half v) {
-  return __half2float(v);
-}
-template <> __device__ __forceinline__ float to_f<__hip_bfloat16>(__hip_bfloat16 v) {
-  return __bfloat162float(v);
-}
-
-template <typename T> __device__ __forceinline__ T from_f(float v);
-template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ __half from_f<__half>(float v) {
-  return __float2half(v);
-}
-template <> __device__ __forceinline__ __hip_bfloat16 from_f<__hip_bfloat16>(float v) {
-  return __float2bfloat16(v);
-}
-
-template <typename T> struct alignas(16) Vec16 {
-  static constexpr int N = 16 / sizeof(T);
-  T v[N];
-};
 
 // ---------------------------------------------------------------------------
 // slot assignment
@@ -343,6 +320,16 @@ void combine_rows_tk(const void* eo, const int* dest, void* out,
 }
 
 template <typename T>
+void combine_rows_t(const void* eo, const int* dest, void* out,
+                    const float* w, int k, int S, size_t R, int M,
+                    hipStream_t stream) {
+  if (k == 1)
+    combine_rows_tk<T, 1>(eo, dest, out, w, S, R, M, stream);
+  else
+    combine_rows_tk<T, 2>(eo, dest, out, w, S, R, M, stream);
+}
+
+template <typename T>
 void row_dot_t(const void* g, const void* eo, const int* dest, float* gw,
                int k, int S, size_t R, int M, hipStream_t stream) {
   const bool vec = ((size_t)M * sizeof(T)) % 16 == 0 && aligned16(g) &&
@@ -360,12 +347,11 @@ void row_dot_t(const void* g, const void* eo, const int* dest, float* gw,
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// launchers (dtype: 0=f32 1=f16 2=bf16)
+// launchers
 // ---------------------------------------------------------------------------
 
 extern "C" {
 
-// number of int32 the caller must provide as `hist` workspace
 size_t bagua_moe_assign_workspace(int S, int E) {
   const size_t nblocks = ((size_t)S + MOE_BLOCK - 1) / MOE_BLOCK;
   return (nblocks ? nblocks : 1) * (size_t)E;
@@ -392,12 +378,8 @@ void bagua_moe_gather_rows_launch(int dtype, const void* x, const int* src,
                                   int k, int S, size_t R, int M,
                                   hipStream_t stream) {
   if (R == 0 || M == 0) return;
-  if (dtype == 0)
-    gather_rows_t<float>(x, src, out, w, dest, k, S, R, M, stream);
-  else if (dtype == 1)
-    gather_rows_t<__half>(x, src, out, w, dest, k, S, R, M, stream);
-  else
-    gather_rows_t<__hip_bfloat16>(x, src, out, w, dest, k, S, R, M, stream);
+  DISPATCH_DTYPE(dtype, __hip_bfloat16, gather_rows_t, x, src, out, w, dest,
+                 k, S, R, M, stream);
 }
 
 void bagua_moe_combine_rows_launch(int dtype, const void* eo,
@@ -405,32 +387,16 @@ void bagua_moe_combine_rows_launch(int dtype, const void* eo,
                                    const float* w, int k, int S, size_t R,
                                    int M, hipStream_t stream) {
   if (S == 0 || M == 0) return;
-#define MOE_COMBINE(T)                                                     \
-  do {                                                                     \
-    if (k == 1)                                                            \
-      combine_rows_tk<T, 1>(eo, dest, out, w, S, R, M, stream);            \
-    else                                                                   \
-      combine_rows_tk<T, 2>(eo, dest, out, w, S, R, M, stream);            \
-  } while (0)
-  if (dtype == 0)
-    MOE_COMBINE(float);
-  else if (dtype == 1)
-    MOE_COMBINE(__half);
-  else
-    MOE_COMBINE(__hip_bfloat16);
-#undef MOE_COMBINE
+  DISPATCH_DTYPE(dtype, __hip_bfloat16, combine_rows_t, eo, dest, out, w, k,
+                 S, R, M, stream);
 }
 
 void bagua_moe_row_dot_launch(int dtype, const void* g, const void* eo,
                               const int* dest, float* gw, int k, int S,
                               size_t R, int M, hipStream_t stream) {
   if (S == 0) return;
-  if (dtype == 0)
-    row_dot_t<float>(g, eo, dest, gw, k, S, R, M, stream);
-  else if (dtype == 1)
-    row_dot_t<__half>(g, eo, dest, gw, k, S, R, M, stream);
-  else
-    row_dot_t<__hip_bfloat16>(g, eo, dest, gw, k, S, R, M, stream);
+  DISPATCH_DTYPE(dtype, __hip_bfloat16, row_dot_t, g, eo, dest, gw, k, S, R,
+                 M, stream);
 }
 
 }  // extern "C"

@@ -23,6 +23,10 @@ ext = cpp_extension.CUDAExtension(
         "bagua_amd/ops/csrc/first_conv_kernels.hip",
         "bagua_amd/ops/csrc/batchnorm_kernels.hip",
     ],
+    depends=[
+        "bagua_amd/ops/csrc/launchers.h",
+        "bagua_amd/ops/csrc/device_util.h",
+    ],
     include_dirs=[os.path.join(ROCM_HOME, "include")],
     libraries=["rccl"],
     library_dirs=[os.path.join(ROCM_HOME, "lib")],
