@@ -55,6 +55,12 @@ class VGG(nn.Module):
     # The fused epilogue's backward leaves the bias gradient to torch's
     # dx.sum((0, 2, 3)) when set: bitwise the unfused result, one more pass.
     torch_bias_grad = False
+    # A pooled stage's full-resolution activation is read by nothing but its
+    # own backward here (the next convolution takes the pooled tensor), so
+    # the epilogue saves a byte per pooled element in its place (kernel path
+    # only; elsewhere the choice changes nothing). False keeps the
+    # activation, as conv_bias_relu does by default; same bits both ways.
+    compact_pool_epilogue = True
 
     def _features(self, x: torch.Tensor) -> torch.Tensor:
         """``self.features(x)``, with every eligible Conv2d -> ReLU
@@ -81,8 +87,12 @@ class VGG(nn.Module):
                 if pool or conv_epilogue.conv_eligible(x, m, False):
                     x = F.conv2d(x, m.weight, None, m.stride, m.padding,
                                  m.dilation, m.groups)
-                    x = conv_epilogue.conv_bias_relu(
-                        x, m.bias, pool, self.torch_bias_grad)
+                    if pool and self.compact_pool_epilogue and x.is_cuda:
+                        x = conv_epilogue.conv_bias_relu_pool(
+                            x, m.bias, self.torch_bias_grad)
+                    else:
+                        x = conv_epilogue.conv_bias_relu(
+                            x, m.bias, pool, self.torch_bias_grad)
                     i += 3 if pool else 2
                     continue
             x = m(x)

@@ -13,6 +13,11 @@ in one pass:
   found again from the saved ``y``; the bias gradient ``sum(dx)`` is
   accumulated on the way.
 
+A pooled stage whose full-resolution ``y`` nobody else reads can drop it
+(``keep_y=False``): the forward then only reads the conv output and writes
+``p`` and a code byte per pooled element (the winner's position and whether
+it was ``<= 0``), and the backward reads that code in place of ``y``.
+
 ``y``, ``p`` and ``dx`` are bit for bit those of the torch chain. The bias
 gradient is a deterministic f32 sum rounded once; its order differs from
 torch's reduction, so it can differ from it in the last bit
@@ -110,19 +115,35 @@ def _channels_last(t: Tensor) -> Tensor:
 
 
 class _ConvBiasRelu(torch.autograd.Function):
-    """apply(conv_out, bias, pool, torch_bias_grad) -> y | (y, p)
+    """apply(conv_out, bias, pool, torch_bias_grad, compact) -> y | (y, p) | p
 
     ``conv_out`` is overwritten with ``y`` (marked dirty: the convolution's
     backward does not need its own output, the liberty an in-place ReLU
     takes too) and saved. autograd wants a dirtied input among the outputs,
-    so with ``pool`` both ``y`` and ``p`` are returned."""
+    so with ``pool`` both ``y`` and ``p`` are returned.
+
+    With ``pool`` and ``compact`` the kernel path leaves ``conv_out`` as it
+    is, returns ``p`` alone and saves one code byte per pooled element in
+    place of ``y``."""
 
     @staticmethod
-    def forward(ctx, conv_out, bias, pool, torch_bias_grad):
+    def forward(ctx, conv_out, bias, pool, torch_bias_grad, compact):
         ctx.set_materialize_grads(False)
         ctx.pool = pool
         ctx.torch_bias_grad = torch_bias_grad
         ctx.native = kernels_apply(conv_out, bias, pool)
+        ctx.compact = bool(compact and pool and ctx.native)
+        if ctx.compact:
+            n, c, h, w = ctx.shape = conv_out.shape
+            p = torch.empty((n, c, h // 2, w // 2), dtype=conv_out.dtype,
+                            device=conv_out.device,
+                            memory_format=torch.channels_last)
+            code = torch.empty((n, h // 2, w // 2, c), dtype=torch.uint8,
+                               device=conv_out.device)
+            native.lib().conv_bias_relu_pool_code(conv_out, bias.detach(), p,
+                                                  code)
+            ctx.save_for_backward(code)
+            return p
         ctx.mark_dirty(conv_out)
         p = idx = None
         if ctx.native:
@@ -150,14 +171,25 @@ class _ConvBiasRelu(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, *grads):
         g = grads[-1]  # of p with pool, of y without
-        if ctx.pool and grads[0] is not None:
+        if ctx.pool and not ctx.compact and grads[0] is not None:
             raise RuntimeError("conv_bias_relu: with pool only the pooled "
                                "output is differentiable")
         if g is None:
-            return None, None, None, None
-        y = ctx.saved_tensors[0]
+            return None, None, None, None, None
         want_db = ctx.needs_input_grad[1]
         db = None
+        if ctx.compact:
+            g = _channels_last(g)
+            dx = torch.empty(ctx.shape, dtype=g.dtype, device=g.device,
+                             memory_format=torch.channels_last)
+            if want_db and not ctx.torch_bias_grad:
+                db = torch.empty(ctx.shape[1], dtype=g.dtype,
+                                 device=g.device)
+            native.lib().conv_pool_code_bwd(g, ctx.saved_tensors[0], dx, db)
+            if want_db and db is None:
+                db = dx.sum((0, 2, 3))
+            return dx, db, None, None, None
+        y = ctx.saved_tensors[0]
         if ctx.native:
             lib = native.lib()
             g = _channels_last(g)
@@ -174,18 +206,35 @@ class _ConvBiasRelu(torch.autograd.Function):
             dx = torch.ops.aten.threshold_backward(g, y, 0)
         if want_db and db is None:
             db = dx.sum((0, 2, 3))
-        return dx, db, None, None
+        return dx, db, None, None, None
 
 
 def conv_bias_relu(conv_out: Tensor, bias: Tensor, pool: bool = False,
-                   torch_bias_grad: bool = False) -> Tensor:
+                   torch_bias_grad: bool = False,
+                   keep_y: bool = True) -> Tensor:
     """``relu(conv_out + bias)``, max-pooled 2x2/stride 2 with ``pool``.
 
     ``conv_out`` (N, C, H, W) is the bias-free convolution result and is
     overwritten; it must not be a leaf that requires grad. Differentiable
     in ``conv_out`` and ``bias``. ``torch_bias_grad`` makes the kernel path
     take the bias gradient from ``dx.sum((0, 2, 3))``, which is bitwise what
-    the unfused chain computes."""
+    the unfused chain computes.
+
+    ``keep_y=False`` matters with ``pool`` only and is for a caller that
+    will not read ``conv_out`` again. The kernel path then neither writes
+    ``y`` there nor saves it: the backward works from one byte per pooled
+    element, and the pooled result, ``dx`` and the bias gradient keep their
+    bits. The torch path overwrites ``conv_out`` as before."""
     out = _ConvBiasRelu.apply(conv_out, bias, bool(pool),
-                              bool(torch_bias_grad))
-    return out[1] if pool else out
+                              bool(torch_bias_grad), not keep_y)
+    return out[1] if isinstance(out, tuple) else out
+
+
+def conv_bias_relu_pool(conv_out: Tensor, bias: Tensor,
+                        torch_bias_grad: bool = False) -> Tensor:
+    """``conv_bias_relu(conv_out, bias, True, torch_bias_grad,
+    keep_y=False)`` under a name of its own, for a model that gives the
+    conv output away."""
+    out = _ConvBiasRelu.apply(conv_out, bias, True, bool(torch_bias_grad),
+                              True)
+    return out[1] if isinstance(out, tuple) else out

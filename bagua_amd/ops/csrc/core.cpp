@@ -1400,6 +1400,52 @@ static void conv_pool_relu_bwd(at::Tensor g, at::Tensor y, at::Tensor dx,
       (int)g.size(3), (int)y.size(1), current_stream());
 }
 
+// the code bytes of the compact pair: one per element of the pooled p
+static void check_epi_code(const at::Tensor& code, const at::Tensor& p) {
+  check_device_contig(code);
+  TORCH_CHECK(code.scalar_type() == at::kByte &&
+                  code.device() == p.device() &&
+                  code.numel() == p.numel(),
+              "code must be uint8 with one element per pooled element, on "
+              "the activation's device");
+  TORCH_CHECK(((uintptr_t)code.data_ptr() & 15u) == 0,
+              "code must be 16-byte aligned");
+}
+
+// p = max_pool2d(relu(x + bias), 2, 2) and the code conv_pool_code_bwd
+// reads; x is left as it is
+static void conv_bias_relu_pool_code(at::Tensor x, at::Tensor bias,
+                                     at::Tensor p, at::Tensor code) {
+  check_epi_act(x, "x");
+  check_epi_bias(bias, x, "bias");
+  check_epi_pooled(p, x, "p");
+  check_epi_code(code, p);
+  bagua_epi_bias_relu_pool_code_launch(
+      kernel_dtype(x), x.data_ptr(), bias.data_ptr(), p.data_ptr(),
+      (uint8_t*)code.data_ptr(),
+      (size_t)(p.size(0) * p.size(2) * p.size(3)), (int)p.size(3),
+      (int)x.size(1), current_stream());
+}
+
+// conv_pool_relu_bwd from the code instead of y
+static void conv_pool_code_bwd(at::Tensor g, at::Tensor code, at::Tensor dx,
+                               std::optional<at::Tensor> db) {
+  check_epi_act(dx, "dx");
+  check_epi_pooled(g, dx, "g");
+  check_epi_code(code, g);
+  const int64_t orows = g.size(0) * g.size(2) * g.size(3);
+  at::Tensor partial;
+  if (db.has_value()) {
+    check_epi_bias(*db, dx, "db");
+    partial = epi_partial(dx, orows);
+  }
+  bagua_epi_pool_code_bwd_launch(
+      kernel_dtype(dx), g.data_ptr(), (const uint8_t*)code.data_ptr(),
+      dx.data_ptr(), db.has_value() ? (float*)partial.data_ptr() : nullptr,
+      db.has_value() ? db->data_ptr() : nullptr, (size_t)orows,
+      (int)g.size(3), (int)dx.size(1), current_stream());
+}
+
 // ---------------------------------------------------------------------------
 // first convolution (first_conv_kernels.hip): Conv2d(3, 64, 3, padding=1)
 // with bias and ReLU on a channels-last bf16 image
@@ -1979,7 +2025,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dx"), py::arg("db") = py::none());
   m.def("conv_pool_relu_bwd", &conv_pool_relu_bwd, py::arg("g"),
         py::arg("y"), py::arg("dx"), py::arg("db") = py::none());
-  m.def("first_conv_bias_relu", &first_conv_bias_relu, py::arg("x"),
+  m.def("conv_bias_relu_pool_code", &conv_bias_relu_pool_code, py::arg("x"),
+        py::arg("bias"), py::arg("p"), py::arg("code"));
+  m.def("conv_pool_code_bwd", &conv_pool_code_bwd, py::arg("g"),
+        py::arg("code"), py::arg("dx"), py::arg("db") = py::none());
+  m.def("first_conv_bias_relu",&first_conv_bias_relu, py::arg("x"),
         py::arg("weight"), py::arg("bias"));
   m.def("first_conv_bias_relu_bwd", &first_conv_bias_relu_bwd, py::arg("g"),
         py::arg("y"), py::arg("x"), py::arg("weight_like"));

@@ -11,6 +11,14 @@
 //   pool_relu_bwd        the pool's winner is found again from y; dx gets g
 //                        there (if y > 0) and 0 elsewhere, db = sum_rows dx
 //
+// and the compact pair, for a stage whose y nothing but its own backward
+// would read:
+//
+//   bias_relu_pool_code  p as above and one code byte per pooled element
+//                        (the winner's position, and whether it was <= 0);
+//                        the conv output is only read
+//   pool_code_bwd        pool_relu_bwd from g and the code, without y
+//
 // Everything but db is bit for bit what the torch chain computes:
 //  * x + b is rounded to T before the ReLU (the in-place add_ did that);
 //    bf16 rounding is torch's (nearest even, every NaN becomes 0x7FC0);
@@ -70,6 +78,15 @@ __device__ __forceinline__ int pool_winner(const T (&y)[4], T& best) {
   }
   return idx;
 }
+
+// What pool_relu_bwd needs of a window's four y: the winner's position in
+// bits 0..1 and, in bit 2, the backward's own `best <= 0` (false for a NaN).
+#define EPI_CODE_DEAD 4
+
+// a lane's N code bytes, stored and loaded as one
+template <int N> struct alignas(N) Bytes {
+  uint8_t v[N];
+};
 
 // A thread's place in the block: channel vector tc, row-lane tr.
 struct Lane {
@@ -200,6 +217,44 @@ epi_bias_relu_pool_kernel(T* __restrict__ x, const T* __restrict__ bias,
   }
 }
 
+// The same window walk; y is formed in registers only and x is not written.
+// code is [orows, C] bytes.
+template <typename T>
+__global__ void __launch_bounds__(EPI_BLOCK) NO_PACKED_F32
+epi_bias_relu_pool_code_kernel(const T* __restrict__ x,
+                               const T* __restrict__ bias, T* __restrict__ p,
+                               uint8_t* __restrict__ code, size_t orows,
+                               uint32_t Wo, int CV, int RL) {
+  using VT = Vec16<T>;
+  constexpr int V = VT::N;
+  const Lane l = lane_of(CV, RL);
+  if (!l.active) return;
+  float b[V];
+  load_bias<T, V>(bias, l.tc, b);
+  const VT* xv = reinterpret_cast<const VT*>(x) + l.tc;
+  VT* pv = reinterpret_cast<VT*>(p) + l.tc;
+  Bytes<V>* cv = reinterpret_cast<Bytes<V>*>(code) + l.tc;
+  const size_t stride = (size_t)gridDim.x * RL;
+  for (size_t o = (size_t)blockIdx.x * RL + l.tr; o < orows; o += stride) {
+    size_t r[4];
+    window_rows(o, Wo, r);
+    VT a[4], out;
+    Bytes<V> cd;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] = xv[r[k] * CV];
+#pragma unroll
+    for (int q = 0; q < V; ++q) {
+      T y[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) y[k] = bias_relu(a[k].v[q], b[q]);
+      const int idx = pool_winner(y, out.v[q]);
+      cd.v[q] = (uint8_t)(idx | (to_f(out.v[q]) <= 0.f ? EPI_CODE_DEAD : 0));
+    }
+    pv[o * CV] = out;
+    cv[o * CV] = cd;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------
@@ -288,6 +343,51 @@ epi_pool_relu_bwd_kernel(const T* __restrict__ g, const T* __restrict__ y,
         const int idx = pool_winner(w, best);
         T d = gg.v[q];  // as it is, -0.0 included
         if (to_f(best) <= 0.f) d = zero;
+        acc[q] += to_f(d);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k].v[q] = (k == idx) ? d : zero;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) dv[r[k] * CV] = a[k];
+    }
+  }
+  if (partial)
+    block_reduce_store<V>(acc, l, CV, RL,
+                          partial + (size_t)blockIdx.x * CV * V);
+}
+
+// epi_pool_relu_bwd_kernel with the winner and its sign read from the code:
+// the same rows per thread and the same order of additions, so db has the
+// same bits.
+template <typename T>
+__global__ void __launch_bounds__(EPI_BLOCK) NO_PACKED_F32
+epi_pool_code_bwd_kernel(const T* __restrict__ g,
+                         const uint8_t* __restrict__ code, T* __restrict__ dx,
+                         float* __restrict__ partial, size_t orows,
+                         uint32_t Wo, int CV, int RL) {
+  using VT = Vec16<T>;
+  constexpr int V = VT::N;
+  const Lane l = lane_of(CV, RL);
+  float acc[V];
+#pragma unroll
+  for (int q = 0; q < V; ++q) acc[q] = 0.f;
+  if (l.active) {
+    const VT* gv = reinterpret_cast<const VT*>(g) + l.tc;
+    const Bytes<V>* cv = reinterpret_cast<const Bytes<V>*>(code) + l.tc;
+    VT* dv = reinterpret_cast<VT*>(dx) + l.tc;
+    const T zero = from_f<T>(0.f);
+    const size_t stride = (size_t)gridDim.x * RL;
+    for (size_t o = (size_t)blockIdx.x * RL + l.tr; o < orows; o += stride) {
+      size_t r[4];
+      window_rows(o, Wo, r);
+      const VT gg = gv[o * CV];
+      const Bytes<V> cd = cv[o * CV];
+      VT a[4];
+#pragma unroll
+      for (int q = 0; q < V; ++q) {
+        const int idx = cd.v[q] & 3;
+        T d = gg.v[q];  // as it is, -0.0 included
+        if (cd.v[q] & EPI_CODE_DEAD) d = zero;
         acc[q] += to_f(d);
 #pragma unroll
         for (int k = 0; k < 4; ++k) a[k].v[q] = (k == idx) ? d : zero;
@@ -408,6 +508,29 @@ void pool_relu_bwd_t(const void* g, const void* y, void* dx, float* partial,
   if (partial) finalize_t<T>(partial, (int)grid, C, db, stream);
 }
 
+template <typename T>
+void bias_relu_pool_code_t(const void* x, const void* bias, void* p,
+                           uint8_t* code, size_t orows, int Wo, int C,
+                           hipStream_t stream) {
+  const Shape s = shape_of<T>(C);
+  hipLaunchKernelGGL((epi_bias_relu_pool_code_kernel<T>),
+                     dim3(grid_for(orows, s.RL, EPI_MAX_GRID)),
+                     dim3(EPI_BLOCK), 0, stream, (const T*)x, (const T*)bias,
+                     (T*)p, code, orows, (uint32_t)Wo, s.CV, s.RL);
+}
+
+template <typename T>
+void pool_code_bwd_t(const void* g, const uint8_t* code, void* dx,
+                     float* partial, void* db, size_t orows, int Wo, int C,
+                     hipStream_t stream) {
+  const Shape s = shape_of<T>(C);
+  const unsigned grid = grid_for(orows, s.RL, reduce_cap(C));
+  hipLaunchKernelGGL((epi_pool_code_bwd_kernel<T>), dim3(grid),
+                     dim3(EPI_BLOCK), 0, stream, (const T*)g, code, (T*)dx,
+                     partial, orows, (uint32_t)Wo, s.CV, s.RL);
+  if (partial) finalize_t<T>(partial, (int)grid, C, db, stream);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -448,6 +571,23 @@ void bagua_epi_pool_relu_bwd_launch(int dtype, const void* g, const void* y,
                                     hipStream_t stream) {
   DISPATCH_DTYPE(dtype, bf16_t, pool_relu_bwd_t, g, y, dx, partial, db, orows,
                  Wo, C, stream);
+}
+
+void bagua_epi_bias_relu_pool_code_launch(int dtype, const void* x,
+                                          const void* bias, void* p,
+                                          uint8_t* code, size_t orows, int Wo,
+                                          int C, hipStream_t stream) {
+  if (orows == 0) return;
+  DISPATCH_DTYPE(dtype, bf16_t, bias_relu_pool_code_t, x, bias, p, code,
+                 orows, Wo, C, stream);
+}
+
+void bagua_epi_pool_code_bwd_launch(int dtype, const void* g,
+                                    const uint8_t* code, void* dx,
+                                    float* partial, void* db, size_t orows,
+                                    int Wo, int C, hipStream_t stream) {
+  DISPATCH_DTYPE(dtype, bf16_t, pool_code_bwd_t, g, code, dx, partial, db,
+                 orows, Wo, C, stream);
 }
 
 }  // extern "C"

@@ -167,6 +167,17 @@ void bagua_epi_pool_relu_bwd_launch(int dtype, const void* g, const void* y,
                                     void* dx, float* partial, void* db,
                                     size_t orows, int Wo, int C,
                                     hipStream_t stream);
+// The compact pair: x is only read; code is [orows, C] bytes, written by the
+// forward for the backward alone, which then needs no y. dx and db are those
+// of the pair above, bit for bit.
+void bagua_epi_bias_relu_pool_code_launch(int dtype, const void* x,
+                                          const void* bias, void* p,
+                                          uint8_t* code, size_t orows, int Wo,
+                                          int C, hipStream_t stream);
+void bagua_epi_pool_code_bwd_launch(int dtype, const void* g,
+                                    const uint8_t* code, void* dx,
+                                    float* partial, void* db, size_t orows,
+                                    int Wo, int C, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // first_conv_kernels.hip. The caller has checked: bf16, x (N, 3, H, W) and

@@ -104,6 +104,47 @@ def sync_batchnorm_rows():
     return rows
 
 
+def conv_epilogue_pool_rows():
+    """The pooled conv epilogue at VGG16's largest pooled stage, 32 x 64 x
+    224 x 224 bf16 channels-last, each kernel alone: the pair that keeps y
+    and the compact pair next to it. Bytes with y the conv output (2 B an
+    element), p and g a quarter of it and the code half of p: keeping y,
+    forward reads and writes y and writes p, backward reads g and y and
+    writes dx; compact, forward reads the conv output and writes p and the
+    code, backward reads g and the code and writes dx."""
+    lib = native.require()
+    cl = dict(memory_format=torch.channels_last)
+    x = torch.randn(32, 64, 224, 224, device="cuda",
+                    dtype=torch.bfloat16).contiguous(**cl)
+    b = torch.randn(64, device="cuda", dtype=torch.bfloat16)
+    p = torch.empty(32, 64, 112, 112, device="cuda",
+                    dtype=torch.bfloat16).contiguous(**cl)
+    g = torch.randn_like(p)
+    code = torch.empty(32, 112, 112, 64, device="cuda", dtype=torch.uint8)
+    dx = torch.empty_like(x)
+    db = torch.empty_like(b)
+    yb, pb, cb = 2 * x.numel(), 2 * p.numel(), code.numel()
+    lib.conv_bias_relu_pool_code(x, b, p, code)
+    rows = []
+    for _ in range(2):  # twice for the spread
+        for label, call, nbytes in (
+                ("epi_pool_code_fwd",
+                 lambda: lib.conv_bias_relu_pool_code(x, b, p, code),
+                 yb + pb + cb),
+                ("epi_pool_code_bwd",
+                 lambda: lib.conv_pool_code_bwd(g, code, dx, db),
+                 pb + cb + yb),
+                # in place: x is relu'd again and again, same work each time
+                ("epi_pool_fwd (keeps y)",
+                 lambda: lib.conv_bias_relu_pool_(x, b, p), 2 * yb + pb),
+                ("epi_pool_bwd (reads y)",
+                 lambda: lib.conv_pool_relu_bwd(g, x, dx, db),
+                 pb + 2 * yb)):
+            gbs, us = bench(call, nbytes)
+            rows.append((label + "@vgg", "bf16", gbs, us))
+    return rows
+
+
 def main():
     lib = native.require()
     n = 1 << 26  # 64 Mi elements
@@ -255,6 +296,7 @@ def main():
     results.append(("first_conv_bwd@vgg", "bf16", gbs, us))
 
     del xi, wt, bs, yo, go
+    results.extend(conv_epilogue_pool_rows())
     results.extend(sync_batchnorm_rows())
 
     print("%-24s %-5s %10s %10s" % ("kernel", "dtype", "GB/s", "us"))
