@@ -10,6 +10,15 @@ On the GPU both directions run as the HIP kernels of ``ops/batchnorm.py``
 around those two allreduces, in the input's memory format (channels-last
 stays channels-last), whenever ``ops.batchnorm.kernels_apply`` takes the
 call; everything else runs the torch formulae below.
+
+``forward(input, residual=None, relu=False)`` is plain batch norm; with
+``relu=True`` it gives ``relu(bn(input))`` or, with a ``residual``,
+``relu(bn(input) + residual)``. In training on the kernel path that is one
+fused function, ``_SyncBatchNormActFn``: the add and the ReLU ride in the
+apply kernel (one rounding, after them), backward reads a sign mask in place
+of the output and writes the residual's gradient along with the input's.
+Wherever the kernels decline, and in eval mode, it is the same torch ops in
+the same order as the unfused composition, bit for bit.
 """
 
 import torch
@@ -33,15 +42,42 @@ class SyncBatchNorm(_BatchNorm):
             raise ValueError("expected at least 2D input (got %dD)"
                              % input.dim())
 
-    def forward(self, input):
+    def forward(self, input, residual=None, relu=False):
+        """``bn(input)``, or with ``relu=True``
+        ``relu(bn(input) [+ residual])``."""
         self._check_input_dim(input)
+        if residual is not None:
+            if not relu:
+                raise ValueError("residual is added before a ReLU: pass "
+                                 "relu=True with it")
+            if (residual.shape != input.shape
+                    or residual.dtype != input.dtype
+                    or residual.device != input.device):
+                raise ValueError(
+                    "residual must have the input's shape, dtype and device "
+                    "(got %s %s on %s for %s %s on %s)"
+                    % (tuple(residual.shape), residual.dtype,
+                       residual.device, tuple(input.shape), input.dtype,
+                       input.device))
         if not self.training and self.track_running_stats:
-            return F.batch_norm(
+            out = F.batch_norm(
                 input, self.running_mean, self.running_var, self.weight,
                 self.bias, False, 0.0, self.eps)
-        return _SyncBatchNormFn.apply(
-            input, self.weight, self.bias, self.running_mean,
-            self.running_var, self.eps, self.momentum)
+        elif relu and bn_ops.kernels_apply(
+                input, self.weight, self.bias, self.running_mean,
+                self.running_var, self.momentum):
+            return _SyncBatchNormActFn.apply(
+                input, residual, self.weight, self.bias, self.running_mean,
+                self.running_var, self.eps, self.momentum)
+        else:
+            out = _SyncBatchNormFn.apply(
+                input, self.weight, self.bias, self.running_mean,
+                self.running_var, self.eps, self.momentum)
+        if relu:
+            if residual is not None:
+                out = out + residual
+            out = torch.relu(out)
+        return out
 
     @classmethod
     def convert_sync_batchnorm(cls, module: torch.nn.Module):
@@ -166,3 +202,40 @@ def _kernel_backward(ctx, grad_output):
             grad_input = bn_ops.backward_apply(
                 grad_output, input, packed, stats, mean_invstd, weight)
     return grad_input, grad_weight, grad_bias, None, None, None, None
+
+
+class _SyncBatchNormActFn(torch.autograd.Function):
+    """``relu(bn(input) [+ residual])`` on the kernel path only: the caller
+    has asked ``bn_ops.kernels_apply``."""
+
+    @staticmethod
+    def forward(ctx, input, residual, weight, bias, running_mean,
+                running_var, eps, momentum):
+        if residual is not None:
+            residual = bn_ops.like_input(residual, input)
+        stats = bn_ops.stats(input)
+        allreduce_inplace(stats, op=ReduceOp.SUM)
+        out, mean_invstd, act = bn_ops.apply_act(
+            input, stats, weight, bias, running_mean, running_var, momentum,
+            eps, residual)
+        # act is the sign mask in the rows layout, where out is not kept
+        ctx.save_for_backward(input, weight, bias, mean_invstd, stats, act)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, weight, bias, mean_invstd, stats, act = ctx.saved_tensors
+        with torch.no_grad():
+            grad_output = bn_ops.like_input(grad_output, input)
+            packed, grad_weight, grad_bias = bn_ops.backward_reduce_act(
+                grad_output, input, act, mean_invstd,
+                weight if ctx.needs_input_grad[2] else None,
+                bias if ctx.needs_input_grad[3] else None)
+            allreduce_inplace(packed, op=ReduceOp.SUM)
+            grad_input = grad_residual = None
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+                grad_input, grad_residual = bn_ops.backward_apply_act(
+                    grad_output, input, act, packed, stats, mean_invstd,
+                    weight, ctx.needs_input_grad[1])
+        return (grad_input, grad_residual, grad_weight, grad_bias, None,
+                None, None, None)

@@ -4,6 +4,22 @@ config (BASELINE.json: ResNet-50 + fused SGD)."""
 import torch
 import torch.nn as nn
 
+from ..contrib.sync_batchnorm import SyncBatchNorm
+
+
+def _bn_act(bn, relu, x, identity=None):
+    """``relu(bn(x))`` or ``relu(bn(x) + identity)``. A SyncBatchNorm takes
+    the add and the ReLU into its own kernels (see ``ResNet.fuse_bn_act``);
+    every other norm, and a ReLU somebody has hooked, runs as modules."""
+    if (ResNet.fuse_bn_act and isinstance(bn, SyncBatchNorm)
+            and not (relu._forward_hooks or relu._forward_pre_hooks
+                     or relu._backward_hooks or relu._backward_pre_hooks)):
+        return bn(x, residual=identity, relu=True)
+    out = bn(x)
+    if identity is not None:
+        out = out + identity
+    return relu(out)
+
 
 class BasicBlock(nn.Module):
     expansion = 1
@@ -19,11 +35,11 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         identity = x
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.bn2(self.conv2(out))
+        out = _bn_act(self.bn1, self.relu, self.conv1(x))
+        out = self.conv2(out)
         if self.downsample is not None:
             identity = self.downsample(x)
-        return self.relu(out + identity)
+        return _bn_act(self.bn2, self.relu, out, identity)
 
 
 class Bottleneck(nn.Module):
@@ -42,15 +58,23 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         identity = x
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
-        out = self.bn3(self.conv3(out))
+        out = _bn_act(self.bn1, self.relu, self.conv1(x))
+        out = _bn_act(self.bn2, self.relu, self.conv2(out))
+        out = self.conv3(out)
         if self.downsample is not None:
             identity = self.downsample(x)
-        return self.relu(out + identity)
+        return _bn_act(self.bn3, self.relu, out, identity)
 
 
 class ResNet(nn.Module):
+    # After SyncBatchNorm.convert_sync_batchnorm, every norm that a ReLU
+    # follows hands the ReLU, and the residual add in front of it, to the
+    # norm's kernels: one rounding after add and ReLU where the modules
+    # round three times, and a sign mask kept for backward in place of the
+    # activation (kernel path only; elsewhere the choice changes nothing).
+    # False runs the modules one by one.
+    fuse_bn_act = True
+
     def __init__(self, block, layers, num_classes=1000):
         super().__init__()
         self.in_planes = 64
@@ -79,7 +103,7 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.maxpool(_bn_act(self.bn1, self.relu, self.conv1(x)))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = torch.flatten(self.avgpool(x), 1)
         return self.fc(x)

@@ -17,6 +17,13 @@ deterministic sums. The kernels of ``csrc/batchnorm_kernels.hip`` see the
 input as rows of channels (4-d channels-last, or inner size 1) or as
 NCHW-contiguous planes; outputs keep the input's memory format.
 
+:func:`apply_act`, :func:`backward_reduce_act` and :func:`backward_apply_act`
+are the same three roles with ``relu(bn(x))`` or ``relu(bn(x) + z)`` fused
+in: the add and the ReLU happen in f32 before the one rounding, backward
+reads the sign of ``y`` (a byte per 16 bytes of it in the rows layout, ``y``
+itself in the planes layout) and writes the residual's gradient in the pass
+that writes ``dx``. :func:`stats` serves both.
+
 :func:`kernels_apply` says whether they take a call (mandatory on a GPU
 machine: a missing extension raises, see ops/native.py); the caller keeps
 its torch path for everything they decline.
@@ -149,3 +156,57 @@ def backward_apply(grad_output: Tensor, input: Tensor, packed: Tensor,
     native.lib().bn_backward_apply(grad_output, input, dx, packed, stats,
                                    mean_invstd, weight)
     return dx
+
+
+def apply_act(input: Tensor, stats: Tensor, weight: Optional[Tensor],
+              bias: Optional[Tensor], running_mean: Optional[Tensor],
+              running_var: Optional[Tensor], momentum: float, eps: float,
+              residual: Optional[Tensor] = None
+              ) -> Tuple[Tensor, Tensor, Tensor]:
+    """:func:`apply` with the activation fused: ``(y, mean_invstd, act)``
+    with ``y = relu(bn(input) [+ residual])``, the add in f32 before the one
+    rounding. ``residual`` is in ``input``'s memory format
+    (:func:`like_input`). ``act`` is what backward needs of ``y``, its sign:
+    in the rows layout a ``uint8`` mask ``[rows, C / V]``, one byte per
+    16-byte vector with bit ``k`` set where element ``k`` of the stored
+    ``y`` is above zero; in the planes layout ``y`` itself."""
+    y = torch.empty_like(input)
+    mean_invstd = _f32(input, 2 * input.shape[1])
+    mask = None
+    if layout_of(input) == "rows":
+        c = input.shape[1]
+        mask = torch.empty(input.numel() // c, c // _vec(input.dtype),
+                           dtype=torch.uint8, device=input.device)
+    native.lib().bn_apply_act(input, y, stats, mean_invstd, weight, bias,
+                              running_mean, running_var, momentum, eps,
+                              residual, mask)
+    return y, mean_invstd, y if mask is None else mask
+
+
+def backward_reduce_act(grad_output: Tensor, input: Tensor, act: Tensor,
+                        mean_invstd: Tensor,
+                        weight: Optional[Tensor] = None,
+                        bias: Optional[Tensor] = None
+                        ) -> Tuple[Tensor, Optional[Tensor],
+                                   Optional[Tensor]]:
+    """:func:`backward_reduce` of ``d = grad_output`` where ``y > 0`` and 0
+    elsewhere, read from :func:`apply_act`'s ``act``."""
+    packed = _f32(input, 2 * input.shape[1])
+    gw = None if weight is None else torch.empty_like(weight)
+    gb = None if bias is None else torch.empty_like(bias)
+    native.lib().bn_backward_reduce_act(grad_output, input, act, mean_invstd,
+                                        packed, gw, gb)
+    return packed, gw, gb
+
+
+def backward_apply_act(grad_output: Tensor, input: Tensor, act: Tensor,
+                       packed: Tensor, stats: Tensor, mean_invstd: Tensor,
+                       weight: Optional[Tensor], want_residual_grad: bool
+                       ) -> Tuple[Tensor, Optional[Tensor]]:
+    """``(dx, dz)``: :func:`backward_apply` of the same ``d``, and, where
+    wanted, ``d`` itself as the residual's gradient, from the same pass."""
+    dx = torch.empty_like(input)
+    dz = torch.empty_like(input) if want_residual_grad else None
+    native.lib().bn_backward_apply_act(grad_output, input, act, dx, packed,
+                                       stats, mean_invstd, weight, dz)
+    return dx, dz

@@ -19,6 +19,21 @@
 //   bn_bwd_apply    dx = (dy - S1/n - (x - mean) * invstd^2 * S2/n)
 //                        * invstd * w
 //
+// An activation can be fused into three of the roles (template parameter
+// ACT: none, ReLU, or add a residual z and ReLU):
+//
+//   bn_apply        y = relu((x - mean) * invstd * w + b [+ z]), the add in
+//                   f32 before the one rounding; NaN passes as in torch.relu
+//   bn_bwd_reduce   the sums of d = (y > 0) ? dy : 0 in place of dy
+//   bn_bwd_apply    dx from d, and dz = d where the residual wants it
+//
+// Backward needs only the sign of the stored y. In the rows layout the
+// forward writes it as one byte per 16-byte vector, [rows, C / V] (bit k
+// is element k of the vector, so f32 uses four bits), from the thread that
+// holds the vector: neighbouring channel lanes write neighbouring bytes,
+// and backward reads a sixteenth of y's bytes. In the planes layout, whose
+// element loads have no natural byte, backward reads y itself.
+//
 // All arithmetic is f32; outputs are rounded once (bf16 as torch rounds).
 // Sums are deterministic, no float atomics: per-thread partial sums, a
 // fixed-order reduction inside the block into its row of a [blocks, 2C] f32
@@ -135,6 +150,15 @@ __device__ __forceinline__ void keep_moments(const Moments& m, int C, int c,
   }
 }
 
+// the activation fused into bn_apply; the backward kernels only know
+// whether there was one (MASKED)
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_ADD_RELU = 2 };
+
+// max(v, 0) that lets NaN through as torch.relu does; fmaxf would drop it
+__device__ __forceinline__ float relu_keep_nan(float v) {
+  return (v > 0.f || v != v) ? v : 0.f;
+}
+
 // ---------------------------------------------------------------------------
 // rows layout
 // ---------------------------------------------------------------------------
@@ -225,8 +249,12 @@ BN_KERNEL bn_rows_stats_kernel(const T* __restrict__ x,
                              partial + (size_t)blockIdx.x * 2 * g.C);
 }
 
-template <typename T>
-BN_KERNEL bn_rows_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
+// ACT != none: z is the residual (add+ReLU only) and mask gets a byte per
+// vector of the stored y, bit k set where element k is above zero.
+template <typename T, int ACT>
+BN_KERNEL bn_rows_apply_kernel(const T* __restrict__ x,
+                               const T* __restrict__ z, T* __restrict__ y,
+                               uint8_t* __restrict__ mask,
                                const float* __restrict__ stats,
                                float* __restrict__ mean_invstd, size_t rows,
                                RowsGeom g, ApplyParams p) {
@@ -247,21 +275,40 @@ BN_KERNEL bn_rows_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
       keep_moments<T>(m, g.C, c, mean_invstd, p);
   }
   const VT* xv = reinterpret_cast<const VT*>(x) + l.cv;
+  const VT* zv = reinterpret_cast<const VT*>(z);
   VT* yv = reinterpret_cast<VT*>(y) + l.cv;
   const size_t stride = (size_t)gridDim.x * g.RL;
 #pragma unroll 4
   for (size_t r = (size_t)blockIdx.x * g.RL + l.tr; r < rows; r += stride) {
     VT a = xv[r * g.CVtot];
+    if constexpr (ACT == ACT_NONE) {
 #pragma unroll
-    for (int k = 0; k < V; ++k)
-      a.v[k] = from_f<T>((to_f(a.v[k]) - mean[k]) * invstd[k] * w[k] + b[k]);
+      for (int k = 0; k < V; ++k)
+        a.v[k] =
+            from_f<T>((to_f(a.v[k]) - mean[k]) * invstd[k] * w[k] + b[k]);
+    } else {
+      VT res;
+      if constexpr (ACT == ACT_ADD_RELU) res = zv[r * g.CVtot + l.cv];
+      unsigned bits = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float v = (to_f(a.v[k]) - mean[k]) * invstd[k] * w[k] + b[k];
+        if constexpr (ACT == ACT_ADD_RELU) v += to_f(res.v[k]);
+        a.v[k] = from_f<T>(relu_keep_nan(v));
+        // the sign of what is stored: a small v may round to zero
+        bits |= (unsigned)(to_f(a.v[k]) > 0.f) << k;
+      }
+      mask[r * g.CVtot + l.cv] = (uint8_t)bits;
+    }
     yv[r * g.CVtot] = a;
   }
 }
 
-template <typename T>
+// MASKED: dy counts only where its bit of the forward's mask is set
+template <typename T, bool MASKED>
 BN_KERNEL bn_rows_bwd_reduce_kernel(const T* __restrict__ dy,
                                     const T* __restrict__ x,
+                                    const uint8_t* __restrict__ mask,
                                     const float* __restrict__ mean_invstd,
                                     float* __restrict__ partial, size_t rows,
                                     RowsGeom g) {
@@ -282,9 +329,12 @@ BN_KERNEL bn_rows_bwd_reduce_kernel(const T* __restrict__ dy,
     for (size_t r = (size_t)blockIdx.x * g.RL + l.tr; r < rows; r += stride) {
       const VT d = gv[r * g.CVtot];
       const VT a = xv[r * g.CVtot];
+      unsigned bits = 0;
+      if constexpr (MASKED) bits = mask[r * g.CVtot + l.cv];
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        const float f = to_f(d.v[k]);
+        float f = to_f(d.v[k]);
+        if constexpr (MASKED) f = (bits >> k & 1u) ? f : 0.f;
         s1[k] += f;
         s2[k] += f * (to_f(a.v[k]) - mean[k]);
       }
@@ -314,10 +364,13 @@ __device__ __forceinline__ BwdCoef bwd_coef(
   return k;
 }
 
-template <typename T>
+// MASKED: as above; the masked dy is also the residual's gradient and is
+// stored to dz where that is not null
+template <typename T, bool MASKED>
 BN_KERNEL bn_rows_bwd_apply_kernel(const T* __restrict__ dy,
                                    const T* __restrict__ x,
-                                   T* __restrict__ dx,
+                                   const uint8_t* __restrict__ mask,
+                                   T* __restrict__ dx, T* __restrict__ dz,
                                    const float* __restrict__ packed,
                                    const float* __restrict__ stats,
                                    const float* __restrict__ mean_invstd,
@@ -340,11 +393,19 @@ BN_KERNEL bn_rows_bwd_apply_kernel(const T* __restrict__ dy,
   const VT* gv = reinterpret_cast<const VT*>(dy) + l.cv;
   const VT* xv = reinterpret_cast<const VT*>(x) + l.cv;
   VT* dv = reinterpret_cast<VT*>(dx) + l.cv;
+  VT* zv = reinterpret_cast<VT*>(dz);
   const size_t stride = (size_t)gridDim.x * g.RL;
 #pragma unroll 2
   for (size_t r = (size_t)blockIdx.x * g.RL + l.tr; r < rows; r += stride) {
     VT d = gv[r * g.CVtot];
     const VT a = xv[r * g.CVtot];
+    if constexpr (MASKED) {
+      const unsigned bits = mask[r * g.CVtot + l.cv];
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        if (!(bits >> k & 1u)) d.v[k] = from_f<T>(0.f);
+      if (dz) zv[r * g.CVtot + l.cv] = d;
+    }
 #pragma unroll
     for (int k = 0; k < V; ++k)
       d.v[k] = from_f<T>(
@@ -433,8 +494,9 @@ BN_KERNEL bn_planes_stats_kernel(const T* __restrict__ x,
   }
 }
 
-template <typename T, int V>
-BN_KERNEL bn_planes_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
+template <typename T, int V, int ACT>
+BN_KERNEL bn_planes_apply_kernel(const T* __restrict__ x,
+                                 const T* __restrict__ z, T* __restrict__ y,
                                  const float* __restrict__ stats,
                                  float* __restrict__ mean_invstd, PlaneGeom g,
                                  ApplyParams p) {
@@ -447,6 +509,7 @@ BN_KERNEL bn_planes_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
   if (blockIdx.y == 0 && threadIdx.x == 0)
     keep_moments<T>(m, (int)g.C, (int)c, mean_invstd, p);
   const VT* xv = reinterpret_cast<const VT*>(x);
+  const VT* zv = reinterpret_cast<const VT*>(z);
   VT* yv = reinterpret_cast<VT*>(y);
   const uint32_t stride = gridDim.y * BN_BLOCK;
 #pragma unroll 4
@@ -454,16 +517,29 @@ BN_KERNEL bn_planes_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
        i += stride) {
     const size_t at = plane_unit(i, c, g);
     VT a = xv[at];
+    if constexpr (ACT == ACT_NONE) {
 #pragma unroll
-    for (int k = 0; k < V; ++k)
-      a.v[k] = from_f<T>((to_f(a.v[k]) - m.mean) * m.invstd * w + b);
+      for (int k = 0; k < V; ++k)
+        a.v[k] = from_f<T>((to_f(a.v[k]) - m.mean) * m.invstd * w + b);
+    } else {
+      VT res;
+      if constexpr (ACT == ACT_ADD_RELU) res = zv[at];
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        float v = (to_f(a.v[k]) - m.mean) * m.invstd * w + b;
+        if constexpr (ACT == ACT_ADD_RELU) v += to_f(res.v[k]);
+        a.v[k] = from_f<T>(relu_keep_nan(v));
+      }
+    }
     yv[at] = a;
   }
 }
 
-template <typename T, int V>
+// MASKED: dy counts only where the forward's output y is above zero
+template <typename T, int V, bool MASKED>
 BN_KERNEL bn_planes_bwd_reduce_kernel(const T* __restrict__ dy,
                                       const T* __restrict__ x,
+                                      const T* __restrict__ y,
                                       const float* __restrict__ mean_invstd,
                                       float* __restrict__ partial,
                                       PlaneGeom g) {
@@ -472,6 +548,7 @@ BN_KERNEL bn_planes_bwd_reduce_kernel(const T* __restrict__ dy,
   const float mean = mean_invstd[c];
   const VT* gv = reinterpret_cast<const VT*>(dy);
   const VT* xv = reinterpret_cast<const VT*>(x);
+  const VT* yv = reinterpret_cast<const VT*>(y);
   float s1[V], s2[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) s1[k] = s2[k] = 0.f;
@@ -482,9 +559,12 @@ BN_KERNEL bn_planes_bwd_reduce_kernel(const T* __restrict__ dy,
     const size_t at = plane_unit(i, c, g);
     const VT d = gv[at];
     const VT a = xv[at];
+    VT o;
+    if constexpr (MASKED) o = yv[at];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const float f = to_f(d.v[k]);
+      float f = to_f(d.v[k]);
+      if constexpr (MASKED) f = to_f(o.v[k]) > 0.f ? f : 0.f;
       s1[k] += f;
       s2[k] += f * (to_f(a.v[k]) - mean);
     }
@@ -497,10 +577,11 @@ BN_KERNEL bn_planes_bwd_reduce_kernel(const T* __restrict__ dy,
   }
 }
 
-template <typename T, int V>
+template <typename T, int V, bool MASKED>
 BN_KERNEL bn_planes_bwd_apply_kernel(const T* __restrict__ dy,
                                      const T* __restrict__ x,
-                                     T* __restrict__ dx,
+                                     const T* __restrict__ y,
+                                     T* __restrict__ dx, T* __restrict__ dz,
                                      const float* __restrict__ packed,
                                      const float* __restrict__ stats,
                                      const float* __restrict__ mean_invstd,
@@ -513,7 +594,9 @@ BN_KERNEL bn_planes_bwd_apply_kernel(const T* __restrict__ dy,
                                  (int)g.C, (int)c);
   const VT* gv = reinterpret_cast<const VT*>(dy);
   const VT* xv = reinterpret_cast<const VT*>(x);
+  const VT* yv = reinterpret_cast<const VT*>(y);
   VT* dv = reinterpret_cast<VT*>(dx);
+  VT* zv = reinterpret_cast<VT*>(dz);
   const uint32_t stride = gridDim.y * BN_BLOCK;
 #pragma unroll 2
   for (uint32_t i = blockIdx.y * BN_BLOCK + threadIdx.x; i < g.M;
@@ -521,6 +604,13 @@ BN_KERNEL bn_planes_bwd_apply_kernel(const T* __restrict__ dy,
     const size_t at = plane_unit(i, c, g);
     VT d = gv[at];
     const VT a = xv[at];
+    if constexpr (MASKED) {
+      const VT o = yv[at];
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        if (!(to_f(o.v[k]) > 0.f)) d.v[k] = from_f<T>(0.f);
+      if (dz) zv[at] = d;
+    }
 #pragma unroll
     for (int k = 0; k < V; ++k)
       d.v[k] = from_f<T>(
@@ -669,55 +759,85 @@ void stats_t(int layout, const void* x, float* partial, float* stats,
                 0, nullptr, 0, stream);
 }
 
-template <typename T>
-void apply_t(int layout, const void* x, void* y, const float* stats,
-             float* mean_invstd, size_t N, int C, size_t S, ApplyParams p,
-             hipStream_t stream) {
+// act: ACT_*; z is the residual of ACT_ADD_RELU, mask the rows layout's
+// sign bytes of ACT_RELU and ACT_ADD_RELU
+template <typename T, int ACT>
+void apply_a(int layout, const void* x, const void* z, void* y, void* mask,
+             const float* stats, float* mean_invstd, size_t N, int C,
+             size_t S, ApplyParams p, hipStream_t stream) {
   constexpr int V = 16 / sizeof(T);
   if (layout == 0) {
     const RowsGeom g = rows_geom<T>(C);
     hipLaunchKernelGGL(
-        (bn_rows_apply_kernel<T>),
+        (bn_rows_apply_kernel<T, ACT>),
         dim3(rows_grid(N, g.RL, BN_APPLY_MAX_GRID), rows_tiles(g)),
-        dim3(BN_BLOCK), 0, stream, (const T*)x, (T*)y, stats, mean_invstd, N,
-        g, p);
+        dim3(BN_BLOCK), 0, stream, (const T*)x, (const T*)z, (T*)y,
+        (uint8_t*)mask, stats, mean_invstd, N, g, p);
   } else if (layout == 1) {
     const PlaneGeom g = plane_geom<1>(N, C, S);
-    hipLaunchKernelGGL((bn_planes_apply_kernel<T, 1>),
+    hipLaunchKernelGGL((bn_planes_apply_kernel<T, 1, ACT>),
                        dim3(C, plane_splits(g.M, C)), dim3(BN_BLOCK), 0,
-                       stream, (const T*)x, (T*)y, stats, mean_invstd, g, p);
+                       stream, (const T*)x, (const T*)z, (T*)y, stats,
+                       mean_invstd, g, p);
   } else {
     const PlaneGeom g = plane_geom<V>(N, C, S);
-    hipLaunchKernelGGL((bn_planes_apply_kernel<T, V>),
+    hipLaunchKernelGGL((bn_planes_apply_kernel<T, V, ACT>),
                        dim3(C, plane_splits(g.M, C)), dim3(BN_BLOCK), 0,
-                       stream, (const T*)x, (T*)y, stats, mean_invstd, g, p);
+                       stream, (const T*)x, (const T*)z, (T*)y, stats,
+                       mean_invstd, g, p);
   }
 }
 
 template <typename T>
-void bwd_reduce_t(int layout, const void* dy, const void* x,
-                  const float* mean_invstd, float* partial, float* packed,
-                  void* gw, int gw_f32, void* gb, int gb_f32, size_t N, int C,
-                  size_t S, hipStream_t stream) {
+void apply_t(int layout, int act, const void* x, const void* z, void* y,
+             void* mask, const float* stats, float* mean_invstd, size_t N,
+             int C, size_t S, ApplyParams p, hipStream_t stream) {
+  switch (act) {
+    case ACT_NONE:
+      apply_a<T, ACT_NONE>(layout, x, z, y, mask, stats, mean_invstd, N, C, S,
+                           p, stream);
+      break;
+    case ACT_RELU:
+      apply_a<T, ACT_RELU>(layout, x, z, y, mask, stats, mean_invstd, N, C, S,
+                           p, stream);
+      break;
+    case ACT_ADD_RELU:
+      apply_a<T, ACT_ADD_RELU>(layout, x, z, y, mask, stats, mean_invstd, N,
+                               C, S, p, stream);
+      break;
+    default:
+      throw std::invalid_argument("unknown batch-norm activation code");
+  }
+}
+
+// saved: what the fused forward kept, the mask bytes (rows) or y (planes)
+template <typename T, bool MASKED>
+void bwd_reduce_m(int layout, const void* dy, const void* x,
+                  const void* saved, const float* mean_invstd, float* partial,
+                  float* packed, void* gw, int gw_f32, void* gb, int gb_f32,
+                  size_t N, int C, size_t S, hipStream_t stream) {
   constexpr int V = 16 / sizeof(T);
   unsigned nrows;
   if (layout == 0) {
     const RowsGeom g = rows_geom<T>(C);
     nrows = rows_grid(N, g.RL, rows_reduce_cap(C));
-    hipLaunchKernelGGL((bn_rows_bwd_reduce_kernel<T>),
+    hipLaunchKernelGGL((bn_rows_bwd_reduce_kernel<T, MASKED>),
                        dim3(nrows, rows_tiles(g)), dim3(BN_BLOCK), 0, stream,
-                       (const T*)dy, (const T*)x, mean_invstd, partial, N, g);
+                       (const T*)dy, (const T*)x, (const uint8_t*)saved,
+                       mean_invstd, partial, N, g);
   } else if (layout == 1) {
     const PlaneGeom g = plane_geom<1>(N, C, S);
     nrows = plane_splits(g.M, C);
-    hipLaunchKernelGGL((bn_planes_bwd_reduce_kernel<T, 1>), dim3(C, nrows),
-                       dim3(BN_BLOCK), 0, stream, (const T*)dy, (const T*)x,
+    hipLaunchKernelGGL((bn_planes_bwd_reduce_kernel<T, 1, MASKED>),
+                       dim3(C, nrows), dim3(BN_BLOCK), 0, stream,
+                       (const T*)dy, (const T*)x, (const T*)saved,
                        mean_invstd, partial, g);
   } else {
     const PlaneGeom g = plane_geom<V>(N, C, S);
     nrows = plane_splits(g.M, C);
-    hipLaunchKernelGGL((bn_planes_bwd_reduce_kernel<T, V>), dim3(C, nrows),
-                       dim3(BN_BLOCK), 0, stream, (const T*)dy, (const T*)x,
+    hipLaunchKernelGGL((bn_planes_bwd_reduce_kernel<T, V, MASKED>),
+                       dim3(C, nrows), dim3(BN_BLOCK), 0, stream,
+                       (const T*)dy, (const T*)x, (const T*)saved,
                        mean_invstd, partial, g);
   }
   finalize_t<T>(partial, nrows, C, packed, 0, 0.f, mean_invstd, gw, gw_f32,
@@ -725,31 +845,60 @@ void bwd_reduce_t(int layout, const void* dy, const void* x,
 }
 
 template <typename T>
-void bwd_apply_t(int layout, const void* dy, const void* x, void* dx,
-                 const float* packed, const float* stats,
+void bwd_reduce_t(int layout, const void* dy, const void* x,
+                  const void* saved, const float* mean_invstd, float* partial,
+                  float* packed, void* gw, int gw_f32, void* gb, int gb_f32,
+                  size_t N, int C, size_t S, hipStream_t stream) {
+  if (saved)
+    bwd_reduce_m<T, true>(layout, dy, x, saved, mean_invstd, partial, packed,
+                          gw, gw_f32, gb, gb_f32, N, C, S, stream);
+  else
+    bwd_reduce_m<T, false>(layout, dy, x, saved, mean_invstd, partial, packed,
+                           gw, gw_f32, gb, gb_f32, N, C, S, stream);
+}
+
+template <typename T, bool MASKED>
+void bwd_apply_m(int layout, const void* dy, const void* x, const void* saved,
+                 void* dx, void* dz, const float* packed, const float* stats,
                  const float* mean_invstd, const void* w, int w_f32, size_t N,
                  int C, size_t S, hipStream_t stream) {
   constexpr int V = 16 / sizeof(T);
   if (layout == 0) {
     const RowsGeom g = rows_geom<T>(C);
     hipLaunchKernelGGL(
-        (bn_rows_bwd_apply_kernel<T>),
+        (bn_rows_bwd_apply_kernel<T, MASKED>),
         dim3(rows_grid(N, g.RL, BN_APPLY_MAX_GRID), rows_tiles(g)),
-        dim3(BN_BLOCK), 0, stream, (const T*)dy, (const T*)x, (T*)dx, packed,
-        stats, mean_invstd, w, w_f32, N, g);
+        dim3(BN_BLOCK), 0, stream, (const T*)dy, (const T*)x,
+        (const uint8_t*)saved, (T*)dx, (T*)dz, packed, stats, mean_invstd, w,
+        w_f32, N, g);
   } else if (layout == 1) {
     const PlaneGeom g = plane_geom<1>(N, C, S);
-    hipLaunchKernelGGL((bn_planes_bwd_apply_kernel<T, 1>),
+    hipLaunchKernelGGL((bn_planes_bwd_apply_kernel<T, 1, MASKED>),
                        dim3(C, plane_splits(g.M, C)), dim3(BN_BLOCK), 0,
-                       stream, (const T*)dy, (const T*)x, (T*)dx, packed,
-                       stats, mean_invstd, w, w_f32, g);
+                       stream, (const T*)dy, (const T*)x, (const T*)saved,
+                       (T*)dx, (T*)dz, packed, stats, mean_invstd, w, w_f32,
+                       g);
   } else {
     const PlaneGeom g = plane_geom<V>(N, C, S);
-    hipLaunchKernelGGL((bn_planes_bwd_apply_kernel<T, V>),
+    hipLaunchKernelGGL((bn_planes_bwd_apply_kernel<T, V, MASKED>),
                        dim3(C, plane_splits(g.M, C)), dim3(BN_BLOCK), 0,
-                       stream, (const T*)dy, (const T*)x, (T*)dx, packed,
-                       stats, mean_invstd, w, w_f32, g);
+                       stream, (const T*)dy, (const T*)x, (const T*)saved,
+                       (T*)dx, (T*)dz, packed, stats, mean_invstd, w, w_f32,
+                       g);
   }
+}
+
+template <typename T>
+void bwd_apply_t(int layout, const void* dy, const void* x, const void* saved,
+                 void* dx, void* dz, const float* packed, const float* stats,
+                 const float* mean_invstd, const void* w, int w_f32, size_t N,
+                 int C, size_t S, hipStream_t stream) {
+  if (saved)
+    bwd_apply_m<T, true>(layout, dy, x, saved, dx, dz, packed, stats,
+                         mean_invstd, w, w_f32, N, C, S, stream);
+  else
+    bwd_apply_m<T, false>(layout, dy, x, saved, dx, dz, packed, stats,
+                          mean_invstd, w, w_f32, N, C, S, stream);
 }
 
 }  // namespace
@@ -779,7 +928,8 @@ void bagua_bn_stats_launch(int dtype, int layout, const void* x,
                  stream);
 }
 
-void bagua_bn_apply_launch(int dtype, int layout, const void* x, void* y,
+void bagua_bn_apply_launch(int dtype, int layout, int act, const void* x,
+                           const void* z, void* y, void* mask,
                            const float* stats, float* mean_invstd,
                            const void* w, int w_f32, const void* b, int b_f32,
                            void* rmean, void* rvar, int r_f32, float momentum,
@@ -796,26 +946,29 @@ void bagua_bn_apply_launch(int dtype, int layout, const void* x, void* y,
   p.momentum = momentum;
   p.one_minus_momentum = one_minus_momentum;
   p.eps = eps;
-  DISPATCH_DTYPE(dtype, bf16_t, apply_t, layout, x, y, stats, mean_invstd, N,
-                 C, S, p, stream);
+  DISPATCH_DTYPE(dtype, bf16_t, apply_t, layout, act, x, z, y, mask, stats,
+                 mean_invstd, N, C, S, p, stream);
 }
 
 void bagua_bn_bwd_reduce_launch(int dtype, int layout, const void* dy,
-                                const void* x, const float* mean_invstd,
-                                float* partial, float* packed, void* gw,
-                                int gw_f32, void* gb, int gb_f32, size_t N,
-                                int C, size_t S, hipStream_t stream) {
-  DISPATCH_DTYPE(dtype, bf16_t, bwd_reduce_t, layout, dy, x, mean_invstd,
-                 partial, packed, gw, gw_f32, gb, gb_f32, N, C, S, stream);
+                                const void* x, const void* saved,
+                                const float* mean_invstd, float* partial,
+                                float* packed, void* gw, int gw_f32, void* gb,
+                                int gb_f32, size_t N, int C, size_t S,
+                                hipStream_t stream) {
+  DISPATCH_DTYPE(dtype, bf16_t, bwd_reduce_t, layout, dy, x, saved,
+                 mean_invstd, partial, packed, gw, gw_f32, gb, gb_f32, N, C,
+                 S, stream);
 }
 
 void bagua_bn_bwd_apply_launch(int dtype, int layout, const void* dy,
-                               const void* x, void* dx, const float* packed,
+                               const void* x, const void* saved, void* dx,
+                               void* dz, const float* packed,
                                const float* stats, const float* mean_invstd,
                                const void* w, int w_f32, size_t N, int C,
                                size_t S, hipStream_t stream) {
-  DISPATCH_DTYPE(dtype, bf16_t, bwd_apply_t, layout, dy, x, dx, packed, stats,
-                 mean_invstd, w, w_f32, N, C, S, stream);
+  DISPATCH_DTYPE(dtype, bf16_t, bwd_apply_t, layout, dy, x, saved, dx, dz,
+                 packed, stats, mean_invstd, w, w_f32, N, C, S, stream);
 }
 
 }  // extern "C"

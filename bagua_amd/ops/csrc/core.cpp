@@ -1644,17 +1644,43 @@ static void bn_stats(at::Tensor x, at::Tensor stats) {
                         (int)v.C, (size_t)v.S, current_stream());
 }
 
-// y = (x - mean) * invstd * weight + bias from the (allreduced) stats;
-// fills mean_invstd [2C] and moves the running statistics in place
-static void bn_apply(at::Tensor x, at::Tensor y, at::Tensor stats,
-                     at::Tensor mean_invstd,
-                     std::optional<at::Tensor> weight,
-                     std::optional<at::Tensor> bias,
-                     std::optional<at::Tensor> running_mean,
-                     std::optional<at::Tensor> running_var, double momentum,
-                     double eps) {
+// What a fused forward leaves for backward: in the rows layout a byte per
+// 16-byte vector of y, [rows, C / vector]; in the planes layout y itself.
+static void* check_bn_saved(const at::Tensor& t, const at::Tensor& x,
+                            BnView& v, const char* what) {
+  if (v.layout != 0) {
+    check_bn_like(t, x, v, what);
+    return t.data_ptr();
+  }
+  check_device_contig(t);
+  TORCH_CHECK(t.scalar_type() == at::kByte && t.device() == x.device() &&
+                  t.numel() * 16 == x.numel() * (int64_t)x.element_size(),
+              what, " must hold a byte per 16 bytes of the activation, on "
+              "its device");
+  return t.data_ptr();
+}
+
+// y = act((x - mean) * invstd * weight + bias [+ residual]) from the
+// (allreduced) stats; fills mean_invstd [2C] and moves the running
+// statistics in place. act 0 is the identity; 1 and 2 are ReLU, and in the
+// rows layout fill `saved` with the sign bytes of y.
+static void bn_apply_impl(int act, const at::Tensor& x, const at::Tensor& y,
+                          const at::Tensor& stats,
+                          const at::Tensor& mean_invstd,
+                          const std::optional<at::Tensor>& weight,
+                          const std::optional<at::Tensor>& bias,
+                          const std::optional<at::Tensor>& running_mean,
+                          const std::optional<at::Tensor>& running_var,
+                          double momentum, double eps,
+                          const std::optional<at::Tensor>& residual,
+                          const std::optional<at::Tensor>& saved) {
   BnView v = check_bn_act(x, "x");
   check_bn_like(y, x, v, "y");
+  if (residual.has_value()) check_bn_like(*residual, x, v, "residual");
+  TORCH_CHECK(saved.has_value() == (act != 0 && v.layout == 0),
+              "the sign bytes go with an activation in the rows layout");
+  void* mask = saved.has_value() ? check_bn_saved(*saved, x, v, "mask")
+                                 : nullptr;
   const float* st = check_bn_f32(stats, 2 * v.C + 1, x, "stats");
   float* mi = check_bn_f32(mean_invstd, 2 * v.C, x, "mean_invstd");
   int w_f32, b_f32, r_f32, rv_f32;
@@ -1664,21 +1690,53 @@ static void bn_apply(at::Tensor x, at::Tensor y, at::Tensor stats,
   void* rv = check_bn_channels(running_var, x, &rv_f32, "running_var");
   TORCH_CHECK((rm == nullptr) == (rv == nullptr) && r_f32 == rv_f32,
               "running_mean and running_var go together, in one dtype");
-  bagua_bn_apply_launch(kernel_dtype(x), v.layout, x.data_ptr(),
-                        y.data_ptr(), st, mi, w, w_f32, b, b_f32, rm, rv,
-                        r_f32, (float)momentum, (float)(1.0 - momentum),
+  bagua_bn_apply_launch(kernel_dtype(x), v.layout, act, x.data_ptr(),
+                        residual.has_value() ? residual->data_ptr() : nullptr,
+                        y.data_ptr(), mask, st, mi, w, w_f32, b, b_f32, rm,
+                        rv, r_f32, (float)momentum, (float)(1.0 - momentum),
                         (float)eps, (size_t)v.N, (int)v.C, (size_t)v.S,
                         current_stream());
 }
 
-// packed = (sum dy [C], sum dy * (x - mean) [C]); from these local sums
-// grad_bias = sum dy and grad_weight = sum dy * (x - mean) * invstd
-static void bn_backward_reduce(at::Tensor dy, at::Tensor x,
-                               at::Tensor mean_invstd, at::Tensor packed,
-                               std::optional<at::Tensor> grad_weight,
-                               std::optional<at::Tensor> grad_bias) {
+static void bn_apply(at::Tensor x, at::Tensor y, at::Tensor stats,
+                     at::Tensor mean_invstd,
+                     std::optional<at::Tensor> weight,
+                     std::optional<at::Tensor> bias,
+                     std::optional<at::Tensor> running_mean,
+                     std::optional<at::Tensor> running_var, double momentum,
+                     double eps) {
+  bn_apply_impl(0, x, y, stats, mean_invstd, weight, bias, running_mean,
+                running_var, momentum, eps, std::nullopt, std::nullopt);
+}
+
+// y = relu(bn(x) [+ residual]); mask is given in the rows layout only
+static void bn_apply_act(at::Tensor x, at::Tensor y, at::Tensor stats,
+                         at::Tensor mean_invstd,
+                         std::optional<at::Tensor> weight,
+                         std::optional<at::Tensor> bias,
+                         std::optional<at::Tensor> running_mean,
+                         std::optional<at::Tensor> running_var,
+                         double momentum, double eps,
+                         std::optional<at::Tensor> residual,
+                         std::optional<at::Tensor> mask) {
+  bn_apply_impl(residual.has_value() ? 2 : 1, x, y, stats, mean_invstd,
+                weight, bias, running_mean, running_var, momentum, eps,
+                residual, mask);
+}
+
+// packed = (sum d [C], sum d * (x - mean) [C]); from these local sums
+// grad_bias = sum d and grad_weight = sum d * (x - mean) * invstd. d is dy,
+// or with `saved` (see check_bn_saved) dy where the fused forward's y is
+// above zero.
+static void bn_backward_reduce_act(at::Tensor dy, at::Tensor x,
+                                   std::optional<at::Tensor> saved,
+                                   at::Tensor mean_invstd, at::Tensor packed,
+                                   std::optional<at::Tensor> grad_weight,
+                                   std::optional<at::Tensor> grad_bias) {
   BnView v = check_bn_act(x, "x");
   check_bn_like(dy, x, v, "dy");
+  const void* sv = saved.has_value() ? check_bn_saved(*saved, x, v, "act")
+                                     : nullptr;
   const float* mi = check_bn_f32(mean_invstd, 2 * v.C, x, "mean_invstd");
   float* pk = check_bn_f32(packed, 2 * v.C, x, "packed");
   int gw_f32, gb_f32;
@@ -1686,28 +1744,53 @@ static void bn_backward_reduce(at::Tensor dy, at::Tensor x,
   void* gb = check_bn_channels(grad_bias, x, &gb_f32, "grad_bias");
   at::Tensor partial = bn_partial(x, v);
   bagua_bn_bwd_reduce_launch(kernel_dtype(x), v.layout, dy.data_ptr(),
-                             x.data_ptr(), mi, (float*)partial.data_ptr(),
+                             x.data_ptr(), sv, mi, (float*)partial.data_ptr(),
                              pk, gw, gw_f32, gb, gb_f32, (size_t)v.N,
                              (int)v.C, (size_t)v.S, current_stream());
 }
 
-// dx from the (allreduced) packed sums and the count in stats[2C]
-static void bn_backward_apply(at::Tensor dy, at::Tensor x, at::Tensor dx,
-                              at::Tensor packed, at::Tensor stats,
-                              at::Tensor mean_invstd,
-                              std::optional<at::Tensor> weight) {
+static void bn_backward_reduce(at::Tensor dy, at::Tensor x,
+                               at::Tensor mean_invstd, at::Tensor packed,
+                               std::optional<at::Tensor> grad_weight,
+                               std::optional<at::Tensor> grad_bias) {
+  bn_backward_reduce_act(dy, x, std::nullopt, mean_invstd, packed,
+                         grad_weight, grad_bias);
+}
+
+// dx from the (allreduced) packed sums and the count in stats[2C]; with
+// `saved`, of the masked dy, which is also stored to dz where given
+static void bn_backward_apply_act(at::Tensor dy, at::Tensor x,
+                                  std::optional<at::Tensor> saved,
+                                  at::Tensor dx, at::Tensor packed,
+                                  at::Tensor stats, at::Tensor mean_invstd,
+                                  std::optional<at::Tensor> weight,
+                                  std::optional<at::Tensor> dz) {
   BnView v = check_bn_act(x, "x");
   check_bn_like(dy, x, v, "dy");
   check_bn_like(dx, x, v, "dx");
+  TORCH_CHECK(saved.has_value() || !dz.has_value(),
+              "dz goes with a fused activation");
+  if (dz.has_value()) check_bn_like(*dz, x, v, "dz");
+  const void* sv = saved.has_value() ? check_bn_saved(*saved, x, v, "act")
+                                     : nullptr;
   const float* pk = check_bn_f32(packed, 2 * v.C, x, "packed");
   const float* st = check_bn_f32(stats, 2 * v.C + 1, x, "stats");
   const float* mi = check_bn_f32(mean_invstd, 2 * v.C, x, "mean_invstd");
   int w_f32;
   const void* w = check_bn_channels(weight, x, &w_f32, "weight");
   bagua_bn_bwd_apply_launch(kernel_dtype(x), v.layout, dy.data_ptr(),
-                            x.data_ptr(), dx.data_ptr(), pk, st, mi, w,
-                            w_f32, (size_t)v.N, (int)v.C, (size_t)v.S,
+                            x.data_ptr(), sv, dx.data_ptr(),
+                            dz.has_value() ? dz->data_ptr() : nullptr, pk, st,
+                            mi, w, w_f32, (size_t)v.N, (int)v.C, (size_t)v.S,
                             current_stream());
+}
+
+static void bn_backward_apply(at::Tensor dy, at::Tensor x, at::Tensor dx,
+                              at::Tensor packed, at::Tensor stats,
+                              at::Tensor mean_invstd,
+                              std::optional<at::Tensor> weight) {
+  bn_backward_apply_act(dy, x, std::nullopt, dx, packed, stats, mean_invstd,
+                        weight, std::nullopt);
 }
 
 static py::bytes nccl_unique_id() {
@@ -2046,4 +2129,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_backward_apply", &bn_backward_apply, py::arg("dy"), py::arg("x"),
         py::arg("dx"), py::arg("packed"), py::arg("stats"),
         py::arg("mean_invstd"), py::arg("weight") = py::none());
+  m.def("bn_apply_act", &bn_apply_act, py::arg("x"), py::arg("y"),
+        py::arg("stats"), py::arg("mean_invstd"),
+        py::arg("weight") = py::none(), py::arg("bias") = py::none(),
+        py::arg("running_mean") = py::none(),
+        py::arg("running_var") = py::none(), py::arg("momentum") = 0.1,
+        py::arg("eps") = 1e-5, py::arg("residual") = py::none(),
+        py::arg("mask") = py::none());
+  m.def("bn_backward_reduce_act", &bn_backward_reduce_act, py::arg("dy"),
+        py::arg("x"), py::arg("act"), py::arg("mean_invstd"),
+        py::arg("packed"), py::arg("grad_weight") = py::none(),
+        py::arg("grad_bias") = py::none());
+  m.def("bn_backward_apply_act", &bn_backward_apply_act, py::arg("dy"),
+        py::arg("x"), py::arg("act"), py::arg("dx"), py::arg("packed"),
+        py::arg("stats"), py::arg("mean_invstd"),
+        py::arg("weight") = py::none(), py::arg("dz") = py::none());
 }

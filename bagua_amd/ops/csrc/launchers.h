@@ -215,22 +215,33 @@ size_t bagua_bn_partial_rows(int dtype, int layout, size_t N, int C,
 void bagua_bn_stats_launch(int dtype, int layout, const void* x,
                            float* partial, float* stats, size_t N, int C,
                            size_t S, hipStream_t stream);
-// w, b and rmean/rvar may be null
-void bagua_bn_apply_launch(int dtype, int layout, const void* x, void* y,
+// w, b and rmean/rvar may be null. act: 0 none, 1 y = relu(bn(x)),
+// 2 y = relu(bn(x) + z). z (act 2 only, else null) is laid out and aligned
+// as x. mask (act 1 and 2 with layout 0 only, else null) receives
+// [N, C / vector] bytes, bit k of a byte set where element k of that
+// 16-byte vector of y is above zero.
+void bagua_bn_apply_launch(int dtype, int layout, int act, const void* x,
+                           const void* z, void* y, void* mask,
                            const float* stats, float* mean_invstd,
                            const void* w, int w_f32, const void* b, int b_f32,
                            void* rmean, void* rvar, int r_f32, float momentum,
                            float one_minus_momentum, float eps, size_t N,
                            int C, size_t S, hipStream_t stream);
-// packed = (sum dy [C], sum dy*(x-mean) [C]); gw and gb may be null
+// packed = (sum dy [C], sum dy*(x-mean) [C]); gw and gb may be null.
+// saved: null, or what a forward with act 1 or 2 left, its mask with layout
+// 0 and its y (laid out and aligned as x) otherwise; dy then counts only
+// where that y is above zero.
 void bagua_bn_bwd_reduce_launch(int dtype, int layout, const void* dy,
-                                const void* x, const float* mean_invstd,
-                                float* partial, float* packed, void* gw,
-                                int gw_f32, void* gb, int gb_f32, size_t N,
-                                int C, size_t S, hipStream_t stream);
-// w may be null
+                                const void* x, const void* saved,
+                                const float* mean_invstd, float* partial,
+                                float* packed, void* gw, int gw_f32, void* gb,
+                                int gb_f32, size_t N, int C, size_t S,
+                                hipStream_t stream);
+// w may be null. saved as above; dz (null without saved, and may be null
+// with it) receives the masked dy, laid out and aligned as x.
 void bagua_bn_bwd_apply_launch(int dtype, int layout, const void* dy,
-                               const void* x, void* dx, const float* packed,
+                               const void* x, const void* saved, void* dx,
+                               void* dz, const float* packed,
                                const float* stats, const float* mean_invstd,
                                const void* w, int w_f32, size_t N, int C,
                                size_t S, hipStream_t stream);

@@ -104,6 +104,65 @@ def sync_batchnorm_rows():
     return rows
 
 
+def sync_batchnorm_act_rows():
+    """relu(bn(x)) and relu(bn(x) + z), forward and backward, at ResNet-50's
+    BN shapes (bf16 channels-last, batch 32): the fused function next to
+    the unfused composition through ``_SyncBatchNormFn`` and torch's add
+    and relu, alternating, twice for the spread; no allreduce in either.
+    Bytes are the fused path's passes in the input's dtype with the sign
+    mask a sixteenth of one: ReLU 3 1/16 forward and 5 1/8 backward,
+    add+ReLU one more each way (read z, write dz); the unfused rows count
+    the same bytes (they move 13 and 16 passes)."""
+    from bagua_amd.contrib import sync_batchnorm
+    from bagua_amd.ops import batchnorm as bn_ops
+
+    rows = []
+    saved = sync_batchnorm.allreduce_inplace
+    sync_batchnorm.allreduce_inplace = lambda t, op=None: None
+    try:
+        for shape in ((32, 64, 112, 112), (32, 256, 56, 56),
+                      (32, 512, 28, 28), (32, 2048, 7, 7)):
+            c = shape[1]
+            tag = "@%dx%dx%dcl" % (c, shape[2], shape[3])
+            x = torch.randn(shape, device="cuda").to(
+                torch.bfloat16).contiguous(memory_format=torch.channels_last)
+            dy, z = torch.randn_like(x), torch.randn_like(x)
+            w = torch.rand(c, device="cuda") + 0.5
+            b = torch.randn(c, device="cuda")
+            rm = torch.zeros(c, device="cuda")
+            rv = torch.ones(c, device="cuda")
+            nbytes = x.numel() * x.element_size()
+            assert bn_ops.kernels_apply(x, w, b, rm, rv, 0.1)
+            for label, res, passes in (("relu", None, 8.1875),
+                                       ("add_relu", z, 10.1875)):
+                leaves = [t.clone().requires_grad_()
+                          for t in (x, w, b) + (() if res is None else (z,))]
+
+                def fused():
+                    y = sync_batchnorm._SyncBatchNormActFn.apply(
+                        leaves[0], leaves[3] if res is not None else None,
+                        leaves[1], leaves[2], rm, rv, 1e-5, 0.1)
+                    return torch.autograd.grad(y, leaves, dy)
+
+                def unfused():
+                    y = sync_batchnorm._SyncBatchNormFn.apply(
+                        leaves[0], leaves[1], leaves[2], rm, rv, 1e-5, 0.1)
+                    if res is not None:
+                        y = y + leaves[3]
+                    return torch.autograd.grad(torch.relu(y), leaves, dy)
+
+                for _ in range(2):
+                    gbs, us = bench(fused, passes * nbytes)
+                    rows.append(("bn_%s fwd+bwd%s" % (label, tag), "bf16",
+                                 gbs, us))
+                    gbs, us = bench(unfused, passes * nbytes)
+                    rows.append(("  unfused bn, %s" % label, "bf16", gbs,
+                                 us))
+    finally:
+        sync_batchnorm.allreduce_inplace = saved
+    return rows
+
+
 def conv_epilogue_pool_rows():
     """The pooled conv epilogue at VGG16's largest pooled stage, 32 x 64 x
     224 x 224 bf16 channels-last, each kernel alone: the pair that keeps y
@@ -298,6 +357,7 @@ def main():
     del xi, wt, bs, yo, go
     results.extend(conv_epilogue_pool_rows())
     results.extend(sync_batchnorm_rows())
+    results.extend(sync_batchnorm_act_rows())
 
     print("%-24s %-5s %10s %10s" % ("kernel", "dtype", "GB/s", "us"))
     for name, dt, gbs, us in results:
