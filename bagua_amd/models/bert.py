@@ -11,6 +11,9 @@ from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
+
+from ..contrib.add_layernorm import FusedDropoutAddLayerNorm
 
 
 @dataclass
@@ -24,6 +27,26 @@ class BertConfig:
     dropout: float = 0.1
 
 
+def _has_hooks(m: nn.Module) -> bool:
+    return bool(m._forward_hooks or m._forward_pre_hooks
+                or m._backward_hooks or m._backward_pre_hooks)
+
+
+def _fused(x, *modules) -> bool:
+    """Whether a sub-layer hands its tail to the norm's kernels (see
+    ``BertForPretrainingShape.fuse_add_ln``): on the GPU, and nobody has
+    hooked a module whose call the fused path leaves out."""
+    return (BertForPretrainingShape.fuse_add_ln and x.is_cuda
+            and not any(_has_hooks(m) for m in modules))
+
+
+def _add_ln(ln, x, inp, lin, drop):
+    """``ln(x + drop(lin(inp)))`` with the bias of ``lin``, the dropout and
+    the add inside the norm: the Linear runs without its bias."""
+    return ln(x, F.linear(inp, lin.weight), lin.bias,
+              drop.p if drop.training else 0.0)
+
+
 class BertSelfAttention(nn.Module):
     def __init__(self, cfg: BertConfig):
         super().__init__()
@@ -33,7 +56,8 @@ class BertSelfAttention(nn.Module):
         self.out = nn.Linear(cfg.hidden_size, cfg.hidden_size)
         self.dropout = nn.Dropout(cfg.dropout)
 
-    def forward(self, x):
+    def context(self, x):
+        """The attention output in front of the ``out`` projection."""
         B, S, H = x.shape
         qkv = self.qkv(x).view(B, S, 3, self.num_heads, self.head_dim)
         q, k, v = qkv.unbind(2)
@@ -42,26 +66,35 @@ class BertSelfAttention(nn.Module):
         v = v.transpose(1, 2)
         # scaled_dot_product_attention lowers to the ROCm fused path on GPU
         y = torch.nn.functional.scaled_dot_product_attention(q, k, v)
-        y = y.transpose(1, 2).reshape(B, S, H)
-        return self.dropout(self.out(y))
+        return y.transpose(1, 2).reshape(B, S, H)
+
+    def forward(self, x):
+        return self.dropout(self.out(self.context(x)))
 
 
 class BertLayer(nn.Module):
     def __init__(self, cfg: BertConfig):
         super().__init__()
         self.attn = BertSelfAttention(cfg)
-        self.ln1 = nn.LayerNorm(cfg.hidden_size)
+        self.ln1 = FusedDropoutAddLayerNorm(cfg.hidden_size)
         self.mlp = nn.Sequential(
             nn.Linear(cfg.hidden_size, cfg.intermediate_size),
             nn.GELU(),
             nn.Linear(cfg.intermediate_size, cfg.hidden_size),
             nn.Dropout(cfg.dropout),
         )
-        self.ln2 = nn.LayerNorm(cfg.hidden_size)
+        self.ln2 = FusedDropoutAddLayerNorm(cfg.hidden_size)
 
     def forward(self, x):
-        x = self.ln1(x + self.attn(x))
-        x = self.ln2(x + self.mlp(x))
+        attn, mlp = self.attn, self.mlp
+        if _fused(x, attn, attn.out, attn.dropout, self.ln1):
+            x = _add_ln(self.ln1, x, attn.context(x), attn.out, attn.dropout)
+        else:
+            x = self.ln1(x + attn(x), kernels=False)
+        if _fused(x, mlp, mlp[2], mlp[3], self.ln2):
+            x = _add_ln(self.ln2, x, mlp[1](mlp[0](x)), mlp[2], mlp[3])
+        else:
+            x = self.ln2(x + mlp(x), kernels=False)
         return x
 
 
@@ -69,13 +102,21 @@ class BertForPretrainingShape(nn.Module):
     """BERT encoder + SQuAD span head; input is token ids, output is
     (start_logits, end_logits)."""
 
+    # Every sub-layer's tail, LayerNorm(x + Dropout(Linear(...))), and the
+    # embedding norm run in the kernels of FusedDropoutAddLayerNorm: the
+    # Linear's bias, the dropout and the add happen in f32 inside the norm's
+    # one pass each way, with the branch in its own dtype (GPU only;
+    # elsewhere the choice changes nothing). False runs the modules one by
+    # one, the norms as nn.LayerNorm.
+    fuse_add_ln = True
+
     def __init__(self, cfg: BertConfig = None):
         super().__init__()
         cfg = cfg or BertConfig()
         self.cfg = cfg
         self.tok_emb = nn.Embedding(cfg.vocab_size, cfg.hidden_size)
         self.pos_emb = nn.Embedding(cfg.max_position, cfg.hidden_size)
-        self.emb_ln = nn.LayerNorm(cfg.hidden_size)
+        self.emb_ln = FusedDropoutAddLayerNorm(cfg.hidden_size)
         self.layers = nn.ModuleList(
             [BertLayer(cfg) for _ in range(cfg.num_layers)])
         self.qa_head = nn.Linear(cfg.hidden_size, 2)
@@ -90,7 +131,8 @@ class BertForPretrainingShape(nn.Module):
     def forward(self, input_ids):
         B, S = input_ids.shape
         pos = torch.arange(S, device=input_ids.device).unsqueeze(0)
-        x = self.emb_ln(self.tok_emb(input_ids) + self.pos_emb(pos))
+        x = self.tok_emb(input_ids) + self.pos_emb(pos)
+        x = self.emb_ln(x, kernels=_fused(x, self.emb_ln))
         for layer in self.layers:
             x = layer(x)
         logits = self.qa_head(x)  # B, S, 2

@@ -1793,6 +1793,167 @@ static void bn_backward_apply(at::Tensor dy, at::Tensor x, at::Tensor dx,
                         weight, std::nullopt);
 }
 
+// ---------------------------------------------------------------------------
+// dropout + residual add + LayerNorm (layernorm_kernels.hip): rows [R, H]
+// ---------------------------------------------------------------------------
+
+// x and everything of its shape and dtype: 2-d, contiguous, aligned
+static void check_ln_rows(const at::Tensor& t, const char* what) {
+  check_device_contig(t);
+  kernel_dtype(t);
+  TORCH_CHECK(t.dim() == 2 && t.numel() > 0 && t.numel() < kInt31 &&
+                  t.size(1) % 8 == 0 && t.size(1) <= BAGUA_LN_HMAX,
+              what, " must be [R, H], not empty, below 2^31 elements, with "
+              "H a multiple of 8 up to ", BAGUA_LN_HMAX);
+  TORCH_CHECK(bn_aligned(t), what, " must be 16-byte aligned");
+}
+
+static void check_ln_like(const at::Tensor& t, const at::Tensor& x,
+                          const char* what) {
+  check_device_contig(t);
+  TORCH_CHECK(t.sizes() == x.sizes() && t.scalar_type() == x.scalar_type() &&
+                  t.device() == x.device() && bn_aligned(t),
+              what, ": shape, dtype, device or alignment mismatch");
+}
+
+// the branch or its gradient: x's shape, in x's dtype or, under an f32 x,
+// f16/bf16
+static void check_ln_branch(const at::Tensor& t, const at::Tensor& x,
+                            const char* what) {
+  check_device_contig(t);
+  kernel_dtype(t);
+  TORCH_CHECK(t.sizes() == x.sizes() && t.device() == x.device() &&
+                  bn_aligned(t) &&
+                  (t.scalar_type() == x.scalar_type() ||
+                   (x.scalar_type() == at::kFloat &&
+                    t.scalar_type() != at::kFloat)),
+              what, " must have x's shape, be aligned, and have x's dtype or "
+              "f16/bf16 under an f32 x");
+}
+
+// optional per-column vector, f32 or in the dtype of `with`
+static void* check_ln_columns(const std::optional<at::Tensor>& t,
+                              const at::Tensor& with, int* is_f32,
+                              const char* what) {
+  *is_f32 = 0;
+  if (!t.has_value()) return nullptr;
+  check_device_contig(*t);
+  TORCH_CHECK(t->dim() == 1 && t->size(0) == with.size(1) &&
+                  t->device() == with.device() &&
+                  (t->scalar_type() == at::kFloat ||
+                   t->scalar_type() == with.scalar_type()),
+              what, " must be 1-d of H elements, f32 or in the dtype of the "
+              "tensor it goes with, on its device");
+  *is_f32 = t->scalar_type() == at::kFloat;
+  return t->data_ptr();
+}
+
+static uint8_t* check_ln_mask(const at::Tensor& t, const at::Tensor& x) {
+  check_device_contig(t);
+  TORCH_CHECK(t.scalar_type() == at::kByte && t.dim() == 2 &&
+                  t.size(0) == x.size(0) && t.size(1) * 8 == x.size(1) &&
+                  t.device() == x.device(),
+              "mask must be [R, H / 8] bytes on x's device");
+  return (uint8_t*)t.data_ptr();
+}
+
+// y = LayerNorm(s), s = x + dropout(h + bias, p); see launchers.h. h, bias,
+// gamma, beta are optional; s is given with h. seed (one int64 in device
+// memory) and mask go with p > 0.
+static void ln_forward(at::Tensor x, std::optional<at::Tensor> h,
+                       std::optional<at::Tensor> bias,
+                       std::optional<at::Tensor> gamma,
+                       std::optional<at::Tensor> beta,
+                       std::optional<at::Tensor> seed, double p, double eps,
+                       at::Tensor y, std::optional<at::Tensor> s,
+                       at::Tensor mean, at::Tensor rstd,
+                       std::optional<at::Tensor> mask) {
+  check_ln_rows(x, "x");
+  check_ln_like(y, x, "y");
+  if (h.has_value()) check_ln_branch(*h, x, "h");
+  TORCH_CHECK(s.has_value() == h.has_value(), "s is stored with a branch");
+  if (s.has_value()) check_ln_like(*s, x, "s");
+  TORCH_CHECK(h.has_value() || !bias.has_value(),
+              "the branch's bias needs the branch");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "p must be in [0, 1)");
+  const bool drop = p > 0.0;
+  TORCH_CHECK(!drop || h.has_value(), "dropout needs the branch");
+  TORCH_CHECK(mask.has_value() == drop && seed.has_value() == drop,
+              "seed and mask go with p > 0");
+  const int64_t* sd = nullptr;
+  if (drop) {
+    check_device_contig(*seed);
+    TORCH_CHECK(seed->scalar_type() == at::kLong && seed->numel() == 1 &&
+                    seed->device() == x.device(),
+                "seed must be one int64 on x's device");
+    sd = (const int64_t*)seed->data_ptr();
+  }
+  const int64_t R = x.size(0), H = x.size(1);
+  float* mp = check_bn_f32(mean, R, x, "mean");
+  float* rp = check_bn_f32(rstd, R, x, "rstd");
+  int bias_f32, gamma_f32, beta_f32;
+  const void* bp =
+      check_ln_columns(bias, h.has_value() ? *h : x, &bias_f32, "bias");
+  const void* gp = check_ln_columns(gamma, x, &gamma_f32, "gamma");
+  const void* ep = check_ln_columns(beta, x, &beta_f32, "beta");
+  const double thr = p * 4294967296.0;  // below 2^32: p < 1 is an f64
+  bagua_ln_fwd_launch(
+      kernel_dtype(x), h.has_value() ? kernel_dtype(*h) : kernel_dtype(x),
+      x.data_ptr(), h.has_value() ? h->data_ptr() : nullptr, bp, bias_f32, gp,
+      gamma_f32, ep, beta_f32, sd,
+      (uint32_t)(thr > 4294967295.0 ? 4294967295.0 : thr),
+      (float)(1.0 / (1.0 - p)), y.data_ptr(),
+      s.has_value() ? s->data_ptr() : nullptr, mp, rp,
+      drop ? check_ln_mask(*mask, x) : nullptr, (float)eps, (size_t)R, (int)H,
+      current_stream());
+}
+
+// dx, and with a branch dh (omitted where it would equal dx: no dropout and
+// one dtype), and whichever of dgamma, dbeta, dbias are given. s is what the
+// forward stored, or x without a branch.
+static void ln_backward(at::Tensor dy, at::Tensor s, at::Tensor mean,
+                        at::Tensor rstd, std::optional<at::Tensor> gamma,
+                        std::optional<at::Tensor> mask, double p,
+                        bool has_branch, at::Tensor dx,
+                        std::optional<at::Tensor> dh,
+                        std::optional<at::Tensor> dgamma,
+                        std::optional<at::Tensor> dbeta,
+                        std::optional<at::Tensor> dbias) {
+  check_ln_rows(s, "s");
+  check_ln_like(dy, s, "dy");
+  check_ln_like(dx, s, "dx");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "p must be in [0, 1)");
+  TORCH_CHECK(mask.has_value() == (p > 0.0), "the mask goes with p > 0");
+  TORCH_CHECK(has_branch || !(mask.has_value() || dh.has_value() ||
+                              dbias.has_value()),
+              "mask, dh and dbias need the branch");
+  if (dh.has_value()) check_ln_branch(*dh, s, "dh");
+  TORCH_CHECK(!mask.has_value() || dh.has_value(),
+              "with dropout dh differs from dx and must be given");
+  const int64_t R = s.size(0), H = s.size(1);
+  const float* mp = check_bn_f32(mean, R, s, "mean");
+  const float* rp = check_bn_f32(rstd, R, s, "rstd");
+  int gamma_f32, dgamma_f32, dbeta_f32, dbias_f32;
+  const void* gp = check_ln_columns(gamma, s, &gamma_f32, "gamma");
+  void* dgp = check_ln_columns(dgamma, s, &dgamma_f32, "dgamma");
+  void* dep = check_ln_columns(dbeta, s, &dbeta_f32, "dbeta");
+  void* dbp = check_ln_columns(dbias, dh.has_value() ? *dh : s, &dbias_f32,
+                               "dbias");
+  at::Tensor partial;
+  if (dgp || dep || dbp)
+    partial = at::empty({(int64_t)bagua_ln_partial_rows((size_t)R), 3 * H},
+                        s.options().dtype(at::kFloat));
+  bagua_ln_bwd_launch(
+      kernel_dtype(s), dh.has_value() ? kernel_dtype(*dh) : kernel_dtype(s),
+      dy.data_ptr(), s.data_ptr(), mp, rp, gp, gamma_f32,
+      mask.has_value() ? check_ln_mask(*mask, s) : nullptr,
+      (float)(1.0 / (1.0 - p)), has_branch ? 1 : 0, dx.data_ptr(),
+      dh.has_value() ? dh->data_ptr() : nullptr,
+      partial.defined() ? (float*)partial.data_ptr() : nullptr, dgp,
+      dgamma_f32, dep, dbeta_f32, dbp, dbias_f32, (size_t)R, (int)H,
+      current_stream());
+}
+
 static py::bytes nccl_unique_id() {
   ncclUniqueId id;
   NCCL_CHECK(ncclGetUniqueId(&id));
@@ -2144,4 +2305,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("act"), py::arg("dx"), py::arg("packed"),
         py::arg("stats"), py::arg("mean_invstd"),
         py::arg("weight") = py::none(), py::arg("dz") = py::none());
+  m.def("ln_forward", &ln_forward, py::arg("x"), py::arg("h"),
+        py::arg("bias"), py::arg("gamma"), py::arg("beta"), py::arg("seed"),
+        py::arg("p"), py::arg("eps"), py::arg("y"), py::arg("s"),
+        py::arg("mean"), py::arg("rstd"), py::arg("mask"));
+  m.def("ln_backward", &ln_backward, py::arg("dy"), py::arg("s"),
+        py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("mask"),
+        py::arg("p"), py::arg("has_branch"), py::arg("dx"), py::arg("dh"),
+        py::arg("dgamma"), py::arg("dbeta"), py::arg("dbias"));
+  m.attr("LN_HMAX") = (int)BAGUA_LN_HMAX;
+  m.attr("LN_WAVES") = (int)BAGUA_LN_WAVES;
+  m.attr("LN_FWD_MAX_GRID") = (int)BAGUA_LN_FWD_MAX_GRID;
 }

@@ -246,4 +246,50 @@ void bagua_bn_bwd_apply_launch(int dtype, int layout, const void* dy,
                                const void* w, int w_f32, size_t N, int C,
                                size_t S, hipStream_t stream);
 
+// ---------------------------------------------------------------------------
+// layernorm_kernels.hip. Rows [R, H], normalised over H:
+//   s = x + keep * (h + bias) * scale,  y = (s - mean) * rstd * gamma + beta
+// x, s, y, dy and dx have the dtype x_dtype; h and dh have h_dtype, which is
+// x_dtype, or f16/bf16 under an f32 x. The caller has checked: H % 8 == 0,
+// 8 <= H <= BAGUA_LN_HMAX, 0 < R * H < 2^31, rows contiguous, every data
+// pointer (x, h, y, s, dy, dx, dh) 16-byte aligned, mask [R, H / 8] bytes,
+// mean and rstd [R] f32. *_f32 say whether a per-column vector is f32; else
+// bias and dbias have h_dtype, gamma, beta and their gradients x_dtype.
+// ---------------------------------------------------------------------------
+
+// longest row, waves (rows in flight) of a block, and the cap on the blocks
+// of the forward kernel, which grid-strides over rows
+#define BAGUA_LN_HMAX 4096
+#define BAGUA_LN_WAVES 4
+#define BAGUA_LN_FWD_MAX_GRID 2048
+
+// h, bias, gamma, beta may be null; h null is plain LayerNorm of x, and then
+// s may be null (it would be x). Dropout happens where mask is not null:
+// seed is one 64-bit word in device memory, an element is kept where its
+// 32 random bits are at or above drop_threshold = p * 2^32, scale is
+// 1 / (1 - p), and mask receives bit k of byte j of a row for element
+// 8 * j + k. Without mask, scale is 1.
+void bagua_ln_fwd_launch(int x_dtype, int h_dtype, const void* x,
+                         const void* h, const void* bias, int bias_f32,
+                         const void* gamma, int gamma_f32, const void* beta,
+                         int beta_f32, const int64_t* seed,
+                         uint32_t drop_threshold, float scale, void* y,
+                         void* s, float* mean, float* rstd, uint8_t* mask,
+                         float eps, size_t R, int H, hipStream_t stream);
+// rows of the f32 partial buffer [rows, 3H] that the backward needs when a
+// column sum is wanted
+size_t bagua_ln_partial_rows(size_t R);
+// dx = ds. With a branch (has_branch), dh = ds * keep * scale where mask is
+// given and ds otherwise; a null dh is not written (the caller uses dx).
+// dgamma, dbeta and dbias are written where not null, dbias only with a
+// branch; partial may be null when all three are.
+void bagua_ln_bwd_launch(int x_dtype, int h_dtype, const void* dy,
+                         const void* s, const float* mean, const float* rstd,
+                         const void* gamma, int gamma_f32,
+                         const uint8_t* mask, float scale, int has_branch,
+                         void* dx, void* dh, float* partial, void* dgamma,
+                         int dgamma_f32, void* dbeta, int dbeta_f32,
+                         void* dbias, int dbias_f32, size_t R, int H,
+                         hipStream_t stream);
+
 }  // extern "C"

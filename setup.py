@@ -22,6 +22,7 @@ ext = cpp_extension.CUDAExtension(
         "bagua_amd/ops/csrc/epilogue_kernels.hip",
         "bagua_amd/ops/csrc/first_conv_kernels.hip",
         "bagua_amd/ops/csrc/batchnorm_kernels.hip",
+        "bagua_amd/ops/csrc/layernorm_kernels.hip",
     ],
     depends=[
         "bagua_amd/ops/csrc/launchers.h",
