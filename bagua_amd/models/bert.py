@@ -14,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..contrib.add_layernorm import FusedDropoutAddLayerNorm
+from ..contrib.bias_gelu import FusedBiasGELU
 
 
 @dataclass
@@ -32,11 +33,11 @@ def _has_hooks(m: nn.Module) -> bool:
                 or m._backward_hooks or m._backward_pre_hooks)
 
 
-def _fused(x, *modules) -> bool:
-    """Whether a sub-layer hands its tail to the norm's kernels (see
-    ``BertForPretrainingShape.fuse_add_ln``): on the GPU, and nobody has
-    hooked a module whose call the fused path leaves out."""
-    return (BertForPretrainingShape.fuse_add_ln and x.is_cuda
+def _fused(x, *modules, flag="fuse_add_ln") -> bool:
+    """Whether a fused path of ``BertForPretrainingShape`` is taken (see its
+    ``fuse_add_ln`` and ``fuse_bias_gelu``): the flag is on, on the GPU, and
+    nobody has hooked a module whose call the fused path leaves out."""
+    return (getattr(BertForPretrainingShape, flag) and x.is_cuda
             and not any(_has_hooks(m) for m in modules))
 
 
@@ -45,6 +46,15 @@ def _add_ln(ln, x, inp, lin, drop):
     the add inside the norm: the Linear runs without its bias."""
     return ln(x, F.linear(inp, lin.weight), lin.bias,
               drop.p if drop.training else 0.0)
+
+
+class _MlpGELU(FusedBiasGELU):
+    """``mlp[1]``. The fused path hands it the first Linear's bias; called
+    without one, as ``nn.Sequential`` calls it, the bias is already in ``h``
+    and this is ``nn.GELU.forward``, the modules one by one."""
+
+    def forward(self, h, bias=None):
+        return super().forward(h, bias, kernels=bias is not None)
 
 
 class BertSelfAttention(nn.Module):
@@ -79,7 +89,7 @@ class BertLayer(nn.Module):
         self.ln1 = FusedDropoutAddLayerNorm(cfg.hidden_size)
         self.mlp = nn.Sequential(
             nn.Linear(cfg.hidden_size, cfg.intermediate_size),
-            nn.GELU(),
+            _MlpGELU(),
             nn.Linear(cfg.intermediate_size, cfg.hidden_size),
             nn.Dropout(cfg.dropout),
         )
@@ -91,11 +101,18 @@ class BertLayer(nn.Module):
             x = _add_ln(self.ln1, x, attn.context(x), attn.out, attn.dropout)
         else:
             x = self.ln1(x + attn(x), kernels=False)
-        if _fused(x, mlp, mlp[2], mlp[3], self.ln2):
-            x = _add_ln(self.ln2, x, mlp[1](mlp[0](x)), mlp[2], mlp[3])
+        gelu = _fused(x, mlp, mlp[0], mlp[1], flag="fuse_bias_gelu")
+        add_ln = _fused(x, mlp, mlp[2], mlp[3], self.ln2)
+        if not (gelu or add_ln):
+            return self.ln2(x + mlp(x), kernels=False)
+        # nobody has hooked mlp itself: its modules by hand
+        if gelu:  # the Linear without its bias, which goes to the activation
+            mid = mlp[1](F.linear(x, mlp[0].weight), mlp[0].bias)
         else:
-            x = self.ln2(x + mlp(x), kernels=False)
-        return x
+            mid = mlp[1](mlp[0](x))
+        if add_ln:
+            return _add_ln(self.ln2, x, mid, mlp[2], mlp[3])
+        return self.ln2(x + mlp[3](mlp[2](mid)), kernels=False)
 
 
 class BertForPretrainingShape(nn.Module):
@@ -109,6 +126,15 @@ class BertForPretrainingShape(nn.Module):
     # elsewhere the choice changes nothing). False runs the modules one by
     # one, the norms as nn.LayerNorm.
     fuse_add_ln = True
+
+    # The middle of every MLP, GELU(Linear(x)), runs in the kernels of
+    # FusedBiasGELU: the first Linear runs without its bias, which is added
+    # in f32 inside the activation's one pass each way, and the backward pass
+    # leaves the bias gradient with it, so that no separate pass over the
+    # gradient sums it (GPU only; elsewhere the choice changes nothing).
+    # False runs the modules one by one, the activation as nn.GELU.
+    # Independent of fuse_add_ln.
+    fuse_bias_gelu = True
 
     def __init__(self, cfg: BertConfig = None):
         super().__init__()

@@ -1954,6 +1954,59 @@ static void ln_backward(at::Tensor dy, at::Tensor s, at::Tensor mean,
       current_stream());
 }
 
+// ---------------------------------------------------------------------------
+// bias + GELU (bias_gelu_kernels.hip): rows [R, C]
+// ---------------------------------------------------------------------------
+
+static void check_bg_rows(const at::Tensor& t, const char* what) {
+  check_device_contig(t);
+  kernel_dtype(t);
+  TORCH_CHECK(t.dim() == 2 && t.numel() > 0 && t.numel() < kInt31 &&
+                  t.size(1) % 8 == 0,
+              what, " must be [R, C], not empty, below 2^31 elements, with "
+              "C a multiple of 8");
+  TORCH_CHECK(bn_aligned(t), what, " must be 16-byte aligned");
+}
+
+// a = gelu(h + bias), erf form or tanh form; see launchers.h
+static void bias_gelu_forward(at::Tensor h, std::optional<at::Tensor> bias,
+                              bool tanh_form, at::Tensor a) {
+  check_bg_rows(h, "h");
+  check_ln_like(a, h, "a");
+  int bias_f32;
+  const void* bp = check_ln_columns(bias, h, &bias_f32, "bias");
+  bagua_bias_gelu_fwd_launch(kernel_dtype(h), tanh_form ? 1 : 0,
+                             h.data_ptr(), bp, bias_f32, a.data_ptr(),
+                             (size_t)h.size(0), (int)h.size(1),
+                             current_stream());
+}
+
+// dh, and dbias where given (it needs the bias)
+static void bias_gelu_backward(at::Tensor dy, at::Tensor h,
+                               std::optional<at::Tensor> bias, bool tanh_form,
+                               at::Tensor dh,
+                               std::optional<at::Tensor> dbias) {
+  check_bg_rows(h, "h");
+  check_ln_like(dy, h, "dy");
+  check_ln_like(dh, h, "dh");
+  TORCH_CHECK(bias.has_value() || !dbias.has_value(),
+              "dbias needs the bias");
+  int bias_f32, dbias_f32;
+  const void* bp = check_ln_columns(bias, h, &bias_f32, "bias");
+  void* dbp = check_ln_columns(dbias, h, &dbias_f32, "dbias");
+  const int64_t R = h.size(0), C = h.size(1);
+  at::Tensor partial;
+  if (dbp)
+    partial = at::empty(
+        {(int64_t)bagua_bias_gelu_partial_rows((size_t)R, (int)C), C},
+        h.options().dtype(at::kFloat));
+  bagua_bias_gelu_bwd_launch(
+      kernel_dtype(h), tanh_form ? 1 : 0, dy.data_ptr(), h.data_ptr(), bp,
+      bias_f32, dh.data_ptr(),
+      partial.defined() ? (float*)partial.data_ptr() : nullptr, dbp,
+      dbias_f32, (size_t)R, (int)C, current_stream());
+}
+
 static py::bytes nccl_unique_id() {
   ncclUniqueId id;
   NCCL_CHECK(ncclGetUniqueId(&id));
@@ -2316,4 +2369,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("LN_HMAX") = (int)BAGUA_LN_HMAX;
   m.attr("LN_WAVES") = (int)BAGUA_LN_WAVES;
   m.attr("LN_FWD_MAX_GRID") = (int)BAGUA_LN_FWD_MAX_GRID;
+  m.def("bias_gelu_forward", &bias_gelu_forward, py::arg("h"),
+        py::arg("bias"), py::arg("tanh_form"), py::arg("a"));
+  m.def("bias_gelu_backward", &bias_gelu_backward, py::arg("dy"),
+        py::arg("h"), py::arg("bias"), py::arg("tanh_form"), py::arg("dh"),
+        py::arg("dbias"));
+  m.def("bias_gelu_partial_rows", [](int64_t R, int64_t C) {
+    TORCH_CHECK(R > 0 && C >= 8 && C % 8 == 0 && R * C < kInt31,
+                "R and C as the kernels take them");
+    return (int64_t)bagua_bias_gelu_partial_rows((size_t)R, (int)C);
+  }, py::arg("R"), py::arg("C"));
+  m.attr("BG_BLOCK") = (int)BAGUA_BG_BLOCK;
+  m.attr("BG_TILE_CHUNKS") = (int)BAGUA_BG_TILE_CHUNKS;
+  m.attr("BG_MAX_GRID") = (int)BAGUA_BG_MAX_GRID;
+  m.attr("BG_PARTIAL_BYTES") = (int64_t)BAGUA_BG_PARTIAL_BYTES;
 }

@@ -292,4 +292,37 @@ void bagua_ln_bwd_launch(int x_dtype, int h_dtype, const void* dy,
                          void* dbias, int dbias_f32, size_t R, int H,
                          hipStream_t stream);
 
+// ---------------------------------------------------------------------------
+// bias_gelu_kernels.hip. Rows [R, C]:
+//   z = h + bias,  a = gelu(z);  dh = dy * gelu'(z),  db = column sums of dh
+// in the erf form, or with tanh_form the tanh form. h, a, dy and dh have the
+// dtype `dtype`. The caller has checked: C % 8 == 0, C >= 8 (no upper
+// limit), 0 < R * C < 2^31, rows contiguous, every data pointer 16-byte
+// aligned. bias may be null (plain GELU); bias_f32 and db_f32 say whether
+// the vector is f32, else it has the data's dtype.
+// ---------------------------------------------------------------------------
+
+// threads of a block; chunks (8 elements) of a row in a column tile, one
+// tile per blockIdx.x; the cap on the blocks of a grid, which grid-strides
+// over rows; and the bound on the backward's f32 partial buffer, which a
+// single row of more than BAGUA_BG_PARTIAL_BYTES / 4 columns exceeds (it is
+// then that one row)
+#define BAGUA_BG_BLOCK 256
+#define BAGUA_BG_TILE_CHUNKS 64
+#define BAGUA_BG_MAX_GRID 1024
+#define BAGUA_BG_PARTIAL_BYTES (2u << 20)
+
+void bagua_bias_gelu_fwd_launch(int dtype, int tanh_form, const void* h,
+                                const void* bias, int bias_f32, void* a,
+                                size_t R, int C, hipStream_t stream);
+// rows of the f32 partial buffer [rows, C] that the backward needs for db
+size_t bagua_bias_gelu_partial_rows(size_t R, int C);
+// db is written where db, bias and partial are all given; without a bias
+// there is nothing to sum
+void bagua_bias_gelu_bwd_launch(int dtype, int tanh_form, const void* dy,
+                                const void* h, const void* bias, int bias_f32,
+                                void* dh, float* partial, void* db,
+                                int db_f32, size_t R, int C,
+                                hipStream_t stream);
+
 }  // extern "C"
