@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from ..contrib.add_layernorm import FusedDropoutAddLayerNorm
 from ..contrib.bias_gelu import FusedBiasGELU
+from ..contrib.self_attention import PackedSelfAttention
 
 
 @dataclass
@@ -35,7 +36,8 @@ def _has_hooks(m: nn.Module) -> bool:
 
 def _fused(x, *modules, flag="fuse_add_ln") -> bool:
     """Whether a fused path of ``BertForPretrainingShape`` is taken (see its
-    ``fuse_add_ln`` and ``fuse_bias_gelu``): the flag is on, on the GPU, and
+    ``fuse_add_ln``, ``fuse_bias_gelu`` and ``fuse_attention``): the flag is
+    on, on the GPU, and
     nobody has hooked a module whose call the fused path leaves out."""
     return (getattr(BertForPretrainingShape, flag) and x.is_cuda
             and not any(_has_hooks(m) for m in modules))
@@ -65,10 +67,16 @@ class BertSelfAttention(nn.Module):
         self.qkv = nn.Linear(cfg.hidden_size, 3 * cfg.hidden_size)
         self.out = nn.Linear(cfg.hidden_size, cfg.hidden_size)
         self.dropout = nn.Dropout(cfg.dropout)
+        self.core = PackedSelfAttention(cfg.num_heads)  # no parameters
 
-    def context(self, x):
-        """The attention output in front of the ``out`` projection."""
+    def context(self, x, seq_lens=None):
+        """The attention output in front of the ``out`` projection. With
+        ``seq_lens`` (``(B,)`` integers on the device of ``x``) keys at or
+        behind a sequence's length are not attended and its rows there come
+        out as zeros."""
         B, S, H = x.shape
+        if seq_lens is not None or _fused(x, flag="fuse_attention"):
+            return self.core(self.qkv(x), seq_lens)
         qkv = self.qkv(x).view(B, S, 3, self.num_heads, self.head_dim)
         q, k, v = qkv.unbind(2)
         q = q.transpose(1, 2)  # B, h, S, d
@@ -78,8 +86,8 @@ class BertSelfAttention(nn.Module):
         y = torch.nn.functional.scaled_dot_product_attention(q, k, v)
         return y.transpose(1, 2).reshape(B, S, H)
 
-    def forward(self, x):
-        return self.dropout(self.out(self.context(x)))
+    def forward(self, x, seq_lens=None):
+        return self.dropout(self.out(self.context(x, seq_lens)))
 
 
 class BertLayer(nn.Module):
@@ -95,12 +103,15 @@ class BertLayer(nn.Module):
         )
         self.ln2 = FusedDropoutAddLayerNorm(cfg.hidden_size)
 
-    def forward(self, x):
+    def forward(self, x, seq_lens=None):
         attn, mlp = self.attn, self.mlp
         if _fused(x, attn, attn.out, attn.dropout, self.ln1):
-            x = _add_ln(self.ln1, x, attn.context(x), attn.out, attn.dropout)
-        else:
+            x = _add_ln(self.ln1, x, attn.context(x, seq_lens), attn.out,
+                        attn.dropout)
+        elif seq_lens is None:
             x = self.ln1(x + attn(x), kernels=False)
+        else:
+            x = self.ln1(x + attn(x, seq_lens), kernels=False)
         gelu = _fused(x, mlp, mlp[0], mlp[1], flag="fuse_bias_gelu")
         add_ln = _fused(x, mlp, mlp[2], mlp[3], self.ln2)
         if not (gelu or add_ln):
@@ -136,6 +147,16 @@ class BertForPretrainingShape(nn.Module):
     # Independent of fuse_add_ln.
     fuse_bias_gelu = True
 
+    # Attention without lengths runs in the kernels of PackedSelfAttention,
+    # which read the qkv Linear's output where it lies and write (B, S, H)
+    # and one packed gradient, in place of scaled_dot_product_attention
+    # between transposed views and a copy back (GPU only, where the kernels
+    # take the shape: f16 or bf16, head_dim 64; elsewhere the choice changes
+    # nothing). False runs that torch chain. With seq_lens given, attention
+    # is PackedSelfAttention whatever this says: the chain has no lengths.
+    # Independent of the two above.
+    fuse_attention = True
+
     def __init__(self, cfg: BertConfig = None):
         super().__init__()
         cfg = cfg or BertConfig()
@@ -154,13 +175,17 @@ class BertForPretrainingShape(nn.Module):
             if isinstance(m, nn.Linear) and m.bias is not None:
                 nn.init.zeros_(m.bias)
 
-    def forward(self, input_ids):
+    def forward(self, input_ids, seq_lens=None):
+        """``seq_lens``: None, or ``(B,)`` integers on the device of
+        ``input_ids``: sequence ``b`` is ``input_ids[b, :seq_lens[b]]`` and
+        what lies behind is padding, which no valid position attends. Logits
+        at padded positions mean nothing."""
         B, S = input_ids.shape
         pos = torch.arange(S, device=input_ids.device).unsqueeze(0)
         x = self.tok_emb(input_ids) + self.pos_emb(pos)
         x = self.emb_ln(x, kernels=_fused(x, self.emb_ln))
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x) if seq_lens is None else layer(x, seq_lens)
         logits = self.qa_head(x)  # B, S, 2
         return logits[..., 0], logits[..., 1]
 

@@ -2007,6 +2007,91 @@ static void bias_gelu_backward(at::Tensor dy, at::Tensor h,
       dbias_f32, (size_t)R, (int)C, current_stream());
 }
 
+// ---------------------------------------------------------------------------
+// self-attention over a packed qkv (attention_kernels.hip)
+// ---------------------------------------------------------------------------
+
+struct AttShape {
+  int B, S, heads;
+};
+
+static AttShape check_att_qkv(const at::Tensor& qkv, int64_t num_heads) {
+  check_device_contig(qkv);
+  TORCH_CHECK(qkv.scalar_type() == at::kHalf ||
+                  qkv.scalar_type() == at::kBFloat16,
+              "qkv must be f16 or bf16");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.numel() > 0 && qkv.numel() < kInt31,
+              "qkv must be (B, S, 3H), not empty, below 2^31 elements");
+  TORCH_CHECK(num_heads >= 1 && num_heads <= 65535 && qkv.size(0) <= 65535 &&
+                  qkv.size(2) == 3 * num_heads * BAGUA_ATT_HEAD_DIM,
+              "qkv must hold (3, num_heads, ", BAGUA_ATT_HEAD_DIM,
+              ") in its last dimension, B and num_heads at most 65535");
+  TORCH_CHECK(bn_aligned(qkv), "qkv must be 16-byte aligned");
+  return {(int)qkv.size(0), (int)qkv.size(1), (int)num_heads};
+}
+
+static void check_att_like(const at::Tensor& t, const at::Tensor& qkv,
+                           int64_t last, const char* what) {
+  check_device_contig(t);
+  TORCH_CHECK(t.device() == qkv.device() &&
+                  t.scalar_type() == qkv.scalar_type() && t.dim() == 3 &&
+                  t.size(0) == qkv.size(0) && t.size(1) == qkv.size(1) &&
+                  t.size(2) == last && bn_aligned(t),
+              what, " must match qkv in device, dtype, B and S, have ", last,
+              " columns and be 16-byte aligned");
+}
+
+static float* check_att_stat(const at::Tensor& t, const at::Tensor& qkv,
+                             const AttShape& s, const char* what) {
+  check_device_contig(t);
+  TORCH_CHECK(t.device() == qkv.device() && t.scalar_type() == at::kFloat &&
+                  t.numel() == (int64_t)s.B * s.heads * s.S,
+              what, " must be f32 (B, num_heads, S) on qkv's device");
+  return (float*)t.data_ptr();
+}
+
+static const int* check_att_lens(const std::optional<at::Tensor>& lens,
+                                 const at::Tensor& qkv) {
+  if (!lens.has_value()) return nullptr;
+  check_device_contig(*lens);
+  TORCH_CHECK(lens->device() == qkv.device() &&
+                  lens->scalar_type() == at::kInt && lens->dim() == 1 &&
+                  lens->size(0) == qkv.size(0),
+              "seq_lens must be int32 (B,) on qkv's device");
+  return (const int*)lens->data_ptr();
+}
+
+// out (B, S, H) and lse (B, num_heads, S); see launchers.h
+static void attention_forward(at::Tensor qkv,
+                              std::optional<at::Tensor> seq_lens,
+                              int64_t num_heads, at::Tensor out,
+                              at::Tensor lse) {
+  const AttShape s = check_att_qkv(qkv, num_heads);
+  check_att_like(out, qkv, qkv.size(2) / 3, "out");
+  float* lp = check_att_stat(lse, qkv, s, "lse");
+  bagua_attention_fwd_launch(kernel_dtype(qkv), qkv.data_ptr(),
+                             check_att_lens(seq_lens, qkv), out.data_ptr(),
+                             lp, s.B, s.S, s.heads, current_stream());
+}
+
+// dqkv (B, S, 3H), written whole
+static void attention_backward(at::Tensor dout, at::Tensor qkv,
+                               at::Tensor out, at::Tensor lse,
+                               std::optional<at::Tensor> seq_lens,
+                               int64_t num_heads, at::Tensor dqkv) {
+  const AttShape s = check_att_qkv(qkv, num_heads);
+  check_att_like(out, qkv, qkv.size(2) / 3, "out");
+  check_att_like(dout, qkv, qkv.size(2) / 3, "dout");
+  check_att_like(dqkv, qkv, qkv.size(2), "dqkv");
+  const float* lp = check_att_stat(lse, qkv, s, "lse");
+  at::Tensor delta = at::empty_like(lse);
+  bagua_attention_bwd_launch(kernel_dtype(qkv), dout.data_ptr(),
+                             qkv.data_ptr(), out.data_ptr(), lp,
+                             check_att_lens(seq_lens, qkv),
+                             (float*)delta.data_ptr(), dqkv.data_ptr(), s.B,
+                             s.S, s.heads, current_stream());
+}
+
 static py::bytes nccl_unique_id() {
   ncclUniqueId id;
   NCCL_CHECK(ncclGetUniqueId(&id));
@@ -2383,4 +2468,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("BG_TILE_CHUNKS") = (int)BAGUA_BG_TILE_CHUNKS;
   m.attr("BG_MAX_GRID") = (int)BAGUA_BG_MAX_GRID;
   m.attr("BG_PARTIAL_BYTES") = (int64_t)BAGUA_BG_PARTIAL_BYTES;
+  m.def("attention_forward", &attention_forward, py::arg("qkv"),
+        py::arg("seq_lens"), py::arg("num_heads"), py::arg("out"),
+        py::arg("lse"));
+  m.def("attention_backward", &attention_backward, py::arg("dout"),
+        py::arg("qkv"), py::arg("out"), py::arg("lse"), py::arg("seq_lens"),
+        py::arg("num_heads"), py::arg("dqkv"));
+  m.attr("ATT_BLOCK_M") = (int)BAGUA_ATT_BLOCK_M;
+  m.attr("ATT_BLOCK_N") = (int)BAGUA_ATT_BLOCK_N;
+  m.attr("ATT_HEAD_DIM") = (int)BAGUA_ATT_HEAD_DIM;
 }

@@ -325,4 +325,31 @@ void bagua_bias_gelu_bwd_launch(int dtype, int tanh_form, const void* dy,
                                 int db_f32, size_t R, int C,
                                 hipStream_t stream);
 
+// ---------------------------------------------------------------------------
+// attention_kernels.hip. Self-attention over a packed qkv (B, S, 3H), last
+// dimension (3, heads, BAGUA_ATT_HEAD_DIM), with a length per sequence:
+// rows at or behind clamp(seq_lens[b], 0, S) are not attended, are never
+// loaded, and come out as zeros in out (B, S, H) and dqkv (B, S, 3H).
+// seq_lens may be null (every length is S). lse and delta are
+// (B, heads, S) f32. The caller has checked: f16 or bf16, everything
+// contiguous, qkv, out, dout and dqkv 16-byte aligned, B, S, heads >= 1,
+// B and heads <= 65535, B * S * 3H < 2^31.
+// ---------------------------------------------------------------------------
+
+// queries a forward block takes and keys it stages at a time; backward uses
+// the same two numbers (its key blocks take BLOCK_M keys and stage BLOCK_N
+// queries)
+#define BAGUA_ATT_BLOCK_M 128
+#define BAGUA_ATT_BLOCK_N 64
+#define BAGUA_ATT_HEAD_DIM 64
+
+void bagua_attention_fwd_launch(int dtype, const void* qkv,
+                                const int* seq_lens, void* out, float* lse,
+                                int B, int S, int heads, hipStream_t stream);
+// delta is workspace; dqkv is written whole, no part of it beforehand
+void bagua_attention_bwd_launch(int dtype, const void* dout, const void* qkv,
+                                const void* out, const float* lse,
+                                const int* seq_lens, float* delta, void* dqkv,
+                                int B, int S, int heads, hipStream_t stream);
+
 }  // extern "C"

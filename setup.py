@@ -24,6 +24,7 @@ ext = cpp_extension.CUDAExtension(
         "bagua_amd/ops/csrc/batchnorm_kernels.hip",
         "bagua_amd/ops/csrc/layernorm_kernels.hip",
         "bagua_amd/ops/csrc/bias_gelu_kernels.hip",
+        "bagua_amd/ops/csrc/attention_kernels.hip",
     ],
     depends=[
         "bagua_amd/ops/csrc/launchers.h",
